@@ -45,7 +45,51 @@ def parse_args(argv=None):
                         "the default; the option remains for launch-bound "
                         "configurations (tiny buffers)")
     p.add_argument("--scalar", type=float, default=2.5)
+    p.add_argument("--seed", type=int, default=0,
+                   help="seed of the input buffers (rank r uses seed + r), so "
+                        "two runs with the same arguments see the same data")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step "
+                        "computed to DIR/<name>.npy (float32): the triad's "
+                        "output buffer `a`, or a fixed seeded sample of it "
+                        "when it is larger than the dump budget")
+    p.add_argument("--full", action="store_true",
+                   help="also run the checks that the headline figure does "
+                        "not need: at N>1 the RCCL transport self-diagnosis "
+                        "(debug-log capture, per-transport channel counts in "
+                        "config.rccl_transports)")
     return p.parse_args(argv)
+
+
+# --dump-outputs budget: 64 MB over all ranks, of which we use a quarter
+DUMP_MAX_ELEMS = (16 << 20) // 4
+
+
+def sample_indices(n, max_elems, seed):
+    """Fixed, seeded sample of positions in a length-n output: everything
+    when it fits, else sorted random positions that always include both
+    ends (same n, max_elems and seed -> same positions in every build)."""
+    import torch
+    if n <= max_elems:
+        return None
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    idx = torch.randint(0, n, (max_elems,), generator=g, dtype=torch.int64)
+    idx[0], idx[-1] = 0, n - 1
+    return idx.sort().values
+
+
+def dump_outputs(out_dir, a, *, rank, world_size, seed):
+    """Write the timed path's output buffer as float32 .npy (one file per
+    rank at N>1, the budget split evenly between ranks)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    idx = sample_indices(a.numel(), DUMP_MAX_ELEMS // world_size, seed)
+    out = a if idx is None else a[idx.to(a.device)]
+    name = "a" if world_size == 1 else f"a_rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"),
+            out.detach().to("cpu", torch.float32).numpy())
 
 
 # multi-GPU self-diagnosis lives in the package so the in-pod payloads
@@ -114,7 +158,7 @@ def main(argv=None) -> int:
     if world_size > 1:
         import torch.distributed as dist_mod
         dist = dist_mod
-        if not rehearsal:
+        if args.full and not rehearsal:
             rccl_log = enable_rccl_debug_capture()
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29571")
@@ -142,6 +186,7 @@ def main(argv=None) -> int:
     if rehearsal:
         buffer_mib = min(buffer_mib, 4)  # keep the dry-run light
     n = buffer_mib * (1 << 20) // 4  # fp32 elements per buffer
+    torch.manual_seed(args.seed + rank)  # same arguments -> same inputs
     b = torch.rand(n, device=device)
     c = torch.rand(n, device=device)
     a = torch.empty_like(b)
@@ -253,6 +298,11 @@ def main(argv=None) -> int:
             if transports and (transports.get("P2P", 0) == 0 or non_p2p):
                 print("# WARNING: RCCL channels not all xGMI P2P — check "
                       "device injection / IPC mode", file=sys.stderr)
+
+    if args.dump_outputs:
+        sync()
+        dump_outputs(args.dump_outputs, a, rank=rank, world_size=world_size,
+                     seed=args.seed)
 
     if rank == 0:
         res = build_result(value=value, n_gpus=n_gpus, steps=args.steps,

@@ -30,6 +30,51 @@ def test_default_args():
     assert args.buffer_mib == 1024
 
 
+def test_plain_run_options_default_off():
+    args = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert args.full is False and args.dump_outputs is None
+    assert args.steps == 3 and args.warmup == 1
+    assert bench.parse_args(["--full"]).full is True
+
+
+def test_sample_indices_fixed_and_bounded():
+    assert bench.sample_indices(100, 100, seed=0) is None  # fits: dump all
+    i1 = bench.sample_indices(1 << 20, 4096, seed=0)
+    i2 = bench.sample_indices(1 << 20, 4096, seed=0)
+    assert i1.tolist() == i2.tolist()
+    assert len(i1) == 4096 and i1[0] == 0 and i1[-1] == (1 << 20) - 1
+    assert bench.DUMP_MAX_ELEMS * 4 <= 64 * 1000 * 1000
+
+
+def test_dump_outputs_reproducible(tmp_path, monkeypatch, capsys):
+    """Same arguments -> same inputs -> identical dumped outputs, in
+    float32, and the dump is the triad of the seeded inputs (CPU rehearsal
+    of the single-process path)."""
+    import numpy as np
+    import torch
+    monkeypatch.setenv("K3SAMD_BENCH_REHEARSAL", "1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    dumps = []
+    for d in ("one", "two"):
+        rc = bench.main(["--gpus", "1", "--steps", "2", "--warmup", "1",
+                         "--buffer-mib", "1", "--dump-outputs",
+                         str(tmp_path / d)])
+        assert rc == 0
+        res = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert res["steps"] == 2 and res["ms_per_step"] >= 0
+        files = sorted(p.name for p in (tmp_path / d).iterdir())
+        assert files == ["a.npy"]
+        dumps.append(np.load(tmp_path / d / "a.npy"))
+    assert dumps[0].dtype == np.float32
+    assert dumps[0].shape == ((1 << 20) // 4,)
+    assert np.array_equal(dumps[0], dumps[1])
+    torch.manual_seed(0)
+    b = torch.rand((1 << 20) // 4)
+    c = torch.rand((1 << 20) // 4)
+    assert np.array_equal(dumps[0], torch.add(b, c, alpha=2.5).numpy())
+
+
 def test_bench_fails_cleanly_without_gpu(repo_root):
     """On a CPU-only box bench.py must exit non-zero with a clear message."""
     import torch
