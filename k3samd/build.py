@@ -36,7 +36,9 @@ def _needs_rebuild() -> bool:
     if not so.exists():
         return True
     so_mtime = so.stat().st_mtime
-    deps = [HIP_SRC, HIP_SRC.parent / "stream_kernels.h"]
+    hip_dir = HIP_SRC.parent
+    deps = [HIP_SRC, hip_dir / "stream_kernels.h",
+            hip_dir / "memtest_kernels.h", hip_dir / "memtest_pattern.h"]
     return any(d.exists() and d.stat().st_mtime > so_mtime for d in deps)
 
 

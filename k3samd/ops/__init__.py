@@ -9,6 +9,8 @@ there is deliberately no silent eager/PyTorch fallback for the compute path
 
 from __future__ import annotations
 
+from dataclasses import dataclass, field
+
 _C = None
 _import_error: Exception | None = None
 
@@ -77,3 +79,79 @@ def mx_gemm16(A, B, fmt=0):
     elements per byte, low nibble = even k: A [16,64], B [16,64]).
     """
     return _require_native().mx_gemm16(A, B, int(fmt))
+
+
+# ---- HBM pattern memory test (kernels in hip/memtest_kernels.h) ----
+
+MEM_PATTERN_ADDR = 0
+MEM_PATTERN_WALK = 1
+MEM_PATTERN_CHECKER = 2
+
+MEM_LOG_SLOTS = 16
+MEM_REPORT_LEN = 8 + 3 * MEM_LOG_SLOTS
+
+_U64 = (1 << 64) - 1
+
+
+@dataclass
+class MemReport:
+    """Host-side view of the device report tensor."""
+
+    bad_dwords: int
+    bad_bits: int
+    first_bad_dword: int | None  # global dword index g = 4*cell + k
+    xor_or: int
+    log: list = field(default_factory=list)  # <= 16 (g, expected, actual)
+
+    @property
+    def clean(self) -> bool:
+        return self.bad_dwords == 0
+
+
+def mem_report_new(device):
+    """Fresh report tensor: int64[56], all zero except first_bad_dword = -1
+    (all-ones, the identity of the unsigned min)."""
+    import torch
+
+    _require_native()
+    r = torch.zeros(MEM_REPORT_LEN, dtype=torch.int64)
+    r[2] = -1
+    return r.to(device)
+
+
+def mem_fill(buf, pattern, seed, invert=False, cell_offset=0,
+             nontemporal=True):
+    """Store the pattern over `buf` (any contiguous GPU tensor whose byte
+    size is a multiple of 16)."""
+    _require_native().mem_fill(buf, int(pattern), int(seed) & _U64,
+                               bool(invert), int(cell_offset) & _U64,
+                               bool(nontemporal))
+
+
+def mem_verify(buf, report, pattern, seed, invert=False, cell_offset=0):
+    """Compare `buf` with the pattern and accumulate into `report`.
+    No host sync: read the report once with mem_report_read()."""
+    _require_native().mem_verify(buf, report, int(pattern), int(seed) & _U64,
+                                 bool(invert), int(cell_offset) & _U64)
+
+
+def mem_verify_fill(buf, report, old, new, cell_offset=0, nontemporal=True):
+    """March element: verify pattern `old` and overwrite with `new` in one
+    pass. `old` and `new` are (pattern, seed, invert) triples."""
+    op, os_, oi = old
+    np_, ns, ni = new
+    _require_native().mem_verify_fill(
+        buf, report, int(op), int(os_) & _U64, bool(oi), int(np_),
+        int(ns) & _U64, bool(ni), int(cell_offset) & _U64, bool(nontemporal))
+
+
+def mem_report_read(report) -> MemReport:
+    """Copy the report to the host (this is the synchronisation point)."""
+    r = [int(v) for v in report.cpu().tolist()]
+    n_log = min(max(r[4], 0), MEM_LOG_SLOTS)
+    log = [(r[8 + 3 * i] & _U64, r[9 + 3 * i] & 0xFFFFFFFF,
+            r[10 + 3 * i] & 0xFFFFFFFF) for i in range(n_log)]
+    first = r[2] & _U64
+    return MemReport(bad_dwords=r[0], bad_bits=r[1],
+                     first_bad_dword=None if first == _U64 else first,
+                     xor_or=r[3] & 0xFFFFFFFF, log=log)

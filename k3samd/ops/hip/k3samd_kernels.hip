@@ -8,6 +8,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "memtest_kernels.h"
 #include "stream_kernels.h"
 
 namespace {
@@ -23,6 +24,35 @@ void check_stream_args(const torch::Tensor& t) {
   K3_CHECK(t.scalar_type() == torch::kFloat32, "tensor must be float32");
   K3_CHECK(t.is_contiguous(), "tensor must be contiguous");
   K3_CHECK(t.numel() % 4 == 0, "numel must be divisible by 4");
+}
+
+// Memory-test target: any contiguous GPU tensor, any dtype, whole 16-byte
+// cells. Shape checks come before the device check so they can be
+// exercised without a GPU; all of them come before any launch.
+int64_t check_mem_buf(const torch::Tensor& t) {
+  K3_CHECK(t.is_contiguous(), "buffer must be contiguous");
+  K3_CHECK(t.nbytes() % 16 == 0, "buffer byte size must be a multiple of 16");
+  K3_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+           "buffer data pointer must be 16-byte aligned");
+  K3_CHECK(t.is_cuda(), "buffer must be on GPU");
+  return (int64_t)(t.nbytes() / 16);
+}
+
+k3samd_kern::MemSpec make_mem_spec(int64_t pattern, uint64_t seed,
+                                   bool invert) {
+  K3_CHECK(pattern >= 0 && pattern < k3samd_kern::kMemPatternCount,
+           "unknown memtest pattern id (0 = ADDR, 1 = WALK, 2 = CHECKER)");
+  return k3samd_kern::MemSpec{seed, (int)pattern, invert ? 1 : 0};
+}
+
+void check_mem_report(const torch::Tensor& report, const torch::Tensor& buf) {
+  K3_CHECK(report.scalar_type() == torch::kInt64, "report must be int64");
+  K3_CHECK(report.dim() == 1 &&
+               report.numel() == k3samd_kern::kMemReportLen &&
+               report.is_contiguous(),
+           "report must be a contiguous int64[56] from mem_report_new()");
+  K3_CHECK(report.is_cuda() && report.device() == buf.device(),
+           "report must be on the same GPU as the buffer");
 }
 
 }  // namespace
@@ -214,6 +244,45 @@ torch::Tensor mx_gemm16(torch::Tensor A, torch::Tensor B, int64_t fmt) {
   return D;
 }
 
+// ---- HBM pattern memory test (memtest_kernels.h) ----
+// None of these synchronise with the host: a multi-pass march queues every
+// step on the current stream and reads the report once at the end.
+
+void mem_fill(torch::Tensor buf, int64_t pattern, uint64_t seed, bool invert,
+              uint64_t cell_offset, bool nontemporal) {
+  auto spec = make_mem_spec(pattern, seed, invert);
+  int64_t n_cells = check_mem_buf(buf);
+  k3samd_kern::launch_mem_fill(at::hip::getCurrentHIPStream(), buf.data_ptr(),
+                               n_cells, cell_offset, spec, nontemporal);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void mem_verify(torch::Tensor buf, torch::Tensor report, int64_t pattern,
+                uint64_t seed, bool invert, uint64_t cell_offset) {
+  auto spec = make_mem_spec(pattern, seed, invert);
+  int64_t n_cells = check_mem_buf(buf);
+  check_mem_report(report, buf);
+  k3samd_kern::launch_mem_verify(at::hip::getCurrentHIPStream(),
+                                 buf.data_ptr(), n_cells, cell_offset, spec,
+                                 report.data_ptr());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void mem_verify_fill(torch::Tensor buf, torch::Tensor report,
+                     int64_t old_pattern, uint64_t old_seed, bool old_invert,
+                     int64_t new_pattern, uint64_t new_seed, bool new_invert,
+                     uint64_t cell_offset, bool nontemporal) {
+  auto old_spec = make_mem_spec(old_pattern, old_seed, old_invert);
+  auto new_spec = make_mem_spec(new_pattern, new_seed, new_invert);
+  int64_t n_cells = check_mem_buf(buf);
+  check_mem_report(report, buf);
+  k3samd_kern::launch_mem_verify_fill(at::hip::getCurrentHIPStream(),
+                                      buf.data_ptr(), n_cells, cell_offset,
+                                      old_spec, new_spec, report.data_ptr(),
+                                      nontemporal);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 // Host-side query: the extension only ships gfx950 code objects, so report
 // whether the active device is gfx950.
 bool has_mfma() {
@@ -241,4 +310,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx_gemm16", &mx_gemm16, py::arg("A"), py::arg("B"),
         py::arg("fmt") = 0);
   m.def("has_mfma", &has_mfma);
+  m.def("mem_fill", &mem_fill, py::arg("buf"), py::arg("pattern"),
+        py::arg("seed"), py::arg("invert") = false,
+        py::arg("cell_offset") = 0, py::arg("nontemporal") = true);
+  m.def("mem_verify", &mem_verify, py::arg("buf"), py::arg("report"),
+        py::arg("pattern"), py::arg("seed"), py::arg("invert") = false,
+        py::arg("cell_offset") = 0);
+  m.def("mem_verify_fill", &mem_verify_fill, py::arg("buf"),
+        py::arg("report"), py::arg("old_pattern"), py::arg("old_seed"),
+        py::arg("old_invert"), py::arg("new_pattern"), py::arg("new_seed"),
+        py::arg("new_invert"), py::arg("cell_offset") = 0,
+        py::arg("nontemporal") = true);
+  m.attr("MEM_REPORT_LEN") = (int64_t)k3samd_kern::kMemReportLen;
 }

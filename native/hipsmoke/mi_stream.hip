@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "../../k3samd/ops/hip/memtest_kernels.h"
 #include "../../k3samd/ops/hip/stream_kernels.h"
 #include "../topology/gpu_health.h"
 #include "../topology/kfd_topology.h"
@@ -159,6 +160,212 @@ bool self_check() {
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// --memtest: HBM pattern memory test (kernels in memtest_kernels.h).
+// Exit codes: 0 clean, 3 detector self-test failed, 4 data miscompare.
+// ---------------------------------------------------------------------------
+
+struct HostMemReport {
+  long long v[k3samd_kern::kMemReportLen];
+  long long bad_dwords() const { return v[0]; }
+  long long bad_bits() const { return v[1]; }
+  unsigned long long first() const { return (unsigned long long)v[2]; }
+  unsigned xor_or() const { return (unsigned)v[3]; }
+  int n_log() const {
+    return v[4] > k3samd_kern::kMemLogSlots ? k3samd_kern::kMemLogSlots
+                                            : (int)v[4];
+  }
+};
+
+int mem_report_reset(void* d_report) {
+  HostMemReport r{};
+  r.v[2] = -1;  // all-ones: identity of the unsigned min
+  HIP_CHECK(hipMemcpy(d_report, r.v, sizeof(r.v), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// XOR `mask` into dword `g` of the buffer with two 4-byte copies.
+int mem_flip(void* buf, uint64_t g, uint32_t mask) {
+  uint32_t w;
+  char* p = static_cast<char*>(buf) + g * 4;
+  HIP_CHECK(hipMemcpy(&w, p, 4, hipMemcpyDeviceToHost));
+  w ^= mask;
+  HIP_CHECK(hipMemcpy(p, &w, 4, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Detector self-test: a detector that has never fired proves nothing.
+// Fill 1 MiB, flip three known bits, verify, and require exactly those
+// three dwords/bits (count, first index, xor-or and log) to come back.
+// Returns 0 ok, 3 detector failed, 1 HIP error.
+int mem_selftest(void* d_report) {
+  using namespace k3samd_kern;
+  const int64_t n_cells = (1 << 20) / 16;
+  const MemSpec spec{0x5EEDF00Dull, kMemPatternAddr, 0};
+  void* buf;
+  HIP_CHECK(hipMalloc(&buf, n_cells * 16));
+  launch_mem_fill(0, buf, n_cells, 0, spec, true);
+  HIP_CHECK(hipDeviceSynchronize());
+  const uint64_t g[3] = {0, 4ull * 12345 + 2, 4ull * n_cells - 1};
+  const uint32_t mask[3] = {1u << 0, 1u << 17, 1u << 31};
+  for (int i = 0; i < 3; ++i)
+    if (mem_flip(buf, g[i], mask[i])) return 1;
+  if (mem_report_reset(d_report)) return 1;
+  launch_mem_verify(0, buf, n_cells, 0, spec, d_report);
+  HIP_CHECK(hipGetLastError());
+  HostMemReport r;
+  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipFree(buf));
+  int caught = 0;
+  for (int i = 0; i < 3; ++i) {
+    const uint32_t expect = memtest_cell(spec, g[i] / 4).d[g[i] % 4];
+    for (int s = 0; s < r.n_log(); ++s) {
+      const long long* rec = r.v + kMemReportHeader + 3 * s;
+      if ((uint64_t)rec[0] == g[i] && (uint32_t)rec[1] == expect &&
+          (uint32_t)rec[2] == (expect ^ mask[i])) {
+        ++caught;
+        break;
+      }
+    }
+  }
+  bool ok = caught == 3 && r.bad_dwords() == 3 && r.bad_bits() == 3 &&
+            r.first() == g[0] && r.v[4] == 3 &&
+            r.xor_or() == (mask[0] | mask[1] | mask[2]);
+  if (!ok) {
+    std::printf("memtest selftest: FAIL (caught %d/3, bad_dwords %lld, "
+                "bad_bits %lld, xor_or 0x%08x)\n",
+                caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
+    return 3;
+  }
+  std::printf("memtest selftest: detector caught 3/3 injected flips\n");
+  return 0;
+}
+
+// Host-side pattern dump (no HIP call): one cell per line, d0..d3 as hex.
+int mem_pattern_dump(char** a) {
+  const int pattern = std::atoi(a[0]);
+  const uint64_t seed = std::strtoull(a[1], nullptr, 0);
+  const bool invert = std::atoi(a[2]) != 0;
+  const uint64_t off = std::strtoull(a[3], nullptr, 0);
+  const uint64_t n = std::strtoull(a[4], nullptr, 0);
+  if (pattern < 0 || pattern >= k3samd_kern::kMemPatternCount) {
+    std::fprintf(stderr, "mi-stream: unknown memtest pattern %d\n", pattern);
+    return 2;
+  }
+  for (uint64_t i = 0; i < n; ++i) {
+    k3samd_kern::MemCell c =
+        k3samd_kern::memtest_cell(pattern, seed, invert, off + i);
+    std::printf("%08x %08x %08x %08x\n", c.d[0], c.d[1], c.d[2], c.d[3]);
+  }
+  return 0;
+}
+
+int run_memtest(int64_t mib, int vram_percent, int passes, int inject,
+                bool do_check) {
+  using namespace k3samd_kern;
+  void* d_report;
+  HIP_CHECK(hipMalloc(&d_report, sizeof(long long) * kMemReportLen));
+  if (do_check) {
+    int rc = mem_selftest(d_report);
+    if (rc) return rc;
+  }
+
+  size_t bytes = (size_t)mib << 20;
+  if (vram_percent > 0) {
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    bytes = (free_b / 100 * (size_t)vram_percent) & ~((size_t)(1 << 20) - 1);
+  }
+  const int64_t n_cells = (int64_t)(bytes / 16);
+  if (n_cells < kMemLogSlots) {
+    std::fprintf(stderr, "mi-stream: memtest buffer too small\n");
+    return 2;
+  }
+  void* buf;
+  HIP_CHECK(hipMalloc(&buf, bytes));
+  hipEvent_t ev0, ev1;
+  HIP_CHECK(hipEventCreate(&ev0));
+  HIP_CHECK(hipEventCreate(&ev1));
+  if (mem_report_reset(d_report)) return 1;
+
+  std::printf("memtest: %.1f MiB, %d pass(es)%s\n", bytes / 1048576.0, passes,
+              inject ? " [fault injection ON]" : "");
+  std::printf("+------+--------------------------------+------------+\n");
+  std::printf("| pass | march step                     |       GB/s |\n");
+  std::printf("+------+--------------------------------+------------+\n");
+  double verify_ms = 0;
+  for (int p = 0; p < passes; ++p) {
+    const uint64_t s = (uint64_t)p;
+    const MemSpec addr{s, kMemPatternAddr, 0}, naddr{s, kMemPatternAddr, 1},
+        walk{s, kMemPatternWalk, 0}, chk{s, kMemPatternChecker, 0};
+    struct Step {
+      const char* name;
+      const MemSpec* from;
+      const MemSpec* to;
+    } steps[] = {
+        {"fill ADDR", nullptr, &addr},
+        {"verify ADDR   -> fill ~ADDR", &addr, &naddr},
+        {"verify ~ADDR  -> fill WALK", &naddr, &walk},
+        {"verify WALK   -> fill CHECKER", &walk, &chk},
+        {"verify CHECKER", &chk, nullptr},
+    };
+    for (const Step& st : steps) {
+      HIP_CHECK(hipEventRecord(ev0));
+      if (!st.from)
+        launch_mem_fill(0, buf, n_cells, 0, *st.to, true);
+      else if (!st.to)
+        launch_mem_verify(0, buf, n_cells, 0, *st.from, d_report);
+      else
+        launch_mem_verify_fill(0, buf, n_cells, 0, *st.from, *st.to, d_report,
+                               true);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(ev1));
+      HIP_CHECK(hipEventSynchronize(ev1));
+      float ms;
+      HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+      const double moved = (st.from && st.to ? 2.0 : 1.0) * (double)bytes;
+      if (st.from && !st.to) verify_ms += ms;
+      std::printf("| %4d | %-30s | %10.1f |\n", p, st.name, gbps(moved, ms));
+      if (!st.from && p == 0 && inject > 0) {
+        // operator alerting drill: N single-bit flips at fixed cells
+        for (int i = 0; i < inject; ++i)
+          if (mem_flip(buf, 4ull * ((uint64_t)i * (n_cells / inject)),
+                       1u << (i % 32)))
+            return 1;
+      }
+    }
+  }
+  std::printf("+------+--------------------------------+------------+\n");
+
+  HostMemReport r;
+  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
+  const bool clean = r.bad_dwords() == 0;
+  const long long first_byte = clean ? -1 : (long long)(r.first() * 4);
+  if (!clean) {
+    std::printf("memtest: MISCOMPARE - %lld dword(s), %lld bit(s)\n",
+                r.bad_dwords(), r.bad_bits());
+    std::printf("%18s %10s %10s %10s\n", "byte offset", "expected", "actual",
+                "xor");
+    for (int i = 0; i < r.n_log(); ++i) {
+      const long long* rec = r.v + kMemReportHeader + 3 * i;
+      std::printf("0x%016llx 0x%08x 0x%08x 0x%08x\n",
+                  (unsigned long long)rec[0] * 4, (unsigned)rec[1],
+                  (unsigned)rec[2], (unsigned)(rec[1] ^ rec[2]));
+    }
+  }
+  std::printf(
+      "{\"payload\": \"mi-memtest\", \"bytes\": %llu, \"passes\": %d, "
+      "\"bad_dwords\": %lld, \"bad_bits\": %lld, \"first_bad_byte\": %lld, "
+      "\"xor_or\": \"0x%08x\", \"verify_gbps\": %.1f, \"mem_clean\": %s}\n",
+      (unsigned long long)bytes, passes, r.bad_dwords(), r.bad_bits(),
+      first_byte, r.xor_or(),
+      verify_ms > 0 ? gbps((double)bytes * passes, (float)verify_ms) : 0.0,
+      clean ? "true" : "false");
+  HIP_CHECK(hipFree(buf));
+  HIP_CHECK(hipFree(d_report));
+  return clean ? 0 : 4;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -171,6 +378,8 @@ int main(int argc, char** argv) {
   bool lds_compare = false;
   bool all_gpus = false;
   int burn_s = 0;
+  bool memtest = false;
+  int passes = 1, vram_percent = 0, inject = 0;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mib") && i + 1 < argc)
       mib = std::atoll(argv[++i]);
@@ -190,11 +399,32 @@ int main(int argc, char** argv) {
       all_gpus = true;
     else if (!std::strcmp(argv[i], "--burn") && i + 1 < argc)
       burn_s = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--memtest"))
+      memtest = true;
+    else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc)
+      passes = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--vram-percent") && i + 1 < argc)
+      vram_percent = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--memtest-inject") && i + 1 < argc)
+      inject = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--memtest-pattern-dump") && i + 5 < argc)
+      return mem_pattern_dump(argv + i + 1);  // host only: before any HIP call
     else {
       std::printf("mi-stream [--mib N] [--iters N] [--device D] [--no-mfma]"
-                  " [--tune] [--lds-compare] [--all-gpus] [--burn SECONDS]\n");
+                  " [--tune] [--lds-compare] [--all-gpus] [--burn SECONDS]"
+                  " [--memtest [--passes N] [--vram-percent P]"
+                  " [--memtest-inject N]] [--memtest-pattern-dump PATTERN"
+                  " SEED INVERT CELL_OFFSET N_CELLS]\n");
       return !std::strcmp(argv[i], "--help") ? 0 : 2;
     }
+  }
+
+  if (memtest &&
+      (passes < 1 || mib < 1 || inject < 0 || inject > 16 ||
+       (vram_percent != 0 && (vram_percent < 1 || vram_percent > 90)))) {
+    std::fprintf(stderr, "mi-stream: --memtest needs --passes >= 1, --mib >= 1,"
+                         " --vram-percent 1..90, --memtest-inject 1..16\n");
+    return 2;
   }
 
   int ndev = 0;
@@ -270,6 +500,9 @@ int main(int argc, char** argv) {
   std::printf("mi-stream: %s (%s), %d visible GPU(s), %d CUs, %.0f GiB VRAM\n",
               gpu_name, prop.gcnArchName, ndev, prop.multiProcessorCount,
               (double)prop.totalGlobalMem / (1 << 30));
+
+  // exit 3: an oracle/self-test failed; exit 4: memtest data miscompare
+  if (memtest) return run_memtest(mib, vram_percent, passes, inject, do_check);
 
   if (do_check && !self_check()) return 3;  // pod log is the oracle
 
