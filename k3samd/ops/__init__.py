@@ -145,6 +145,41 @@ def mem_verify_fill(buf, report, old, new, cell_offset=0, nontemporal=True):
         int(ns) & _U64, bool(ni), int(cell_offset) & _U64, bool(nontemporal))
 
 
+# ---- verified bf16 MFMA GEMM (kernels in hip/gemm_kernels.h) ----
+
+GEMM_TILE_M = 128
+GEMM_TILE_N = 128
+GEMM_TILE_K = 64
+GEMM_EXACT_MAX_K = 32768  # 256 * K <= 2^23: every partial sum exact in fp32
+
+
+def gemm_fill(buf, which, seed, rows, cols):
+    """Write generator operands as bf16 into the stored [rows, cols] matrix
+    `buf`: which = 0 is A[M,K]; which = 1 is Bt[N,K], whose element [n][k]
+    is gemm_operand(seed, 1, row=k, col=n)."""
+    _require_native().gemm_fill(buf, int(which), int(seed) & _U64, int(rows),
+                                int(cols))
+
+
+def gemm_bf16_nt(A, Bt, out=None, where=None):
+    """C[M,N] (fp32) = A[M,K] @ Bt[N,K].T with v_mfma_f32_16x16x32_bf16,
+    for any bf16 data. M % 128 == N % 128 == K % 64 == 0. `where`
+    (int32 [tiles, 2]) receives each 128x128 tile's XCC_ID and HW_ID."""
+    return _require_native().gemm_bf16_nt(A, Bt, out, where)
+
+
+def gemm_ref_int(A, Bt, out=None):
+    """The same product by int32 VALU arithmetic (no MFMA), as fp32. For
+    operands holding integers in [-128, 127], K <= 32768."""
+    return _require_native().gemm_ref_int(A, Bt, out)
+
+
+def buf_compare(buf, expected, report):
+    """Bitwise compare of two equally sized GPU buffers, accumulated into
+    a mem_report_new() report; dword indices count 32-bit elements."""
+    _require_native().buf_compare(buf, expected, report)
+
+
 def mem_report_read(report) -> MemReport:
     """Copy the report to the host (this is the synchronisation point)."""
     r = [int(v) for v in report.cpu().tolist()]

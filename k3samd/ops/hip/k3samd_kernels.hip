@@ -8,6 +8,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "gemm_kernels.h"
 #include "memtest_kernels.h"
 #include "stream_kernels.h"
 
@@ -53,6 +54,50 @@ void check_mem_report(const torch::Tensor& report, const torch::Tensor& buf) {
            "report must be a contiguous int64[56] from mem_report_new()");
   K3_CHECK(report.is_cuda() && report.device() == buf.device(),
            "report must be on the same GPU as the buffer");
+}
+
+// Verified-GEMM operands: A [M,K] and Bt [N,K], bf16, contiguous, 16-byte
+// aligned, meeting gemm_bf16_nt_kernel's shape contract. Everything that
+// does not need the device is checked before the device check.
+struct GemmDims {
+  int64_t m, n, k;
+};
+
+GemmDims check_gemm_operands(const torch::Tensor& A, const torch::Tensor& Bt) {
+  K3_CHECK(A.scalar_type() == torch::kBFloat16 &&
+               Bt.scalar_type() == torch::kBFloat16,
+           "A and Bt must be bfloat16");
+  K3_CHECK(A.dim() == 2 && Bt.dim() == 2, "A must be [M,K] and Bt [N,K]");
+  K3_CHECK(A.is_contiguous() && Bt.is_contiguous(),
+           "A and Bt must be contiguous");
+  K3_CHECK(A.size(1) == Bt.size(1), "A [M,K] and Bt [N,K] disagree on K");
+  GemmDims d{A.size(0), Bt.size(0), A.size(1)};
+  K3_CHECK(k3samd_kern::gemm_shape_ok(d.m, d.n, d.k),
+           "gemm shape contract: M % 128 == 0, N % 128 == 0, K % 64 == 0, "
+           "all > 0");
+  K3_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(Bt.data_ptr()) % 16 == 0,
+           "A and Bt data pointers must be 16-byte aligned");
+  K3_CHECK(A.is_cuda() && Bt.is_cuda(), "A and Bt must be on GPU");
+  K3_CHECK(A.device() == Bt.device(), "A and Bt must be on the same GPU");
+  return d;
+}
+
+// fp32 [M,N] result buffer: the caller's `out` after checks, or a new one.
+torch::Tensor gemm_result(const c10::optional<torch::Tensor>& out,
+                          const torch::Tensor& A, const GemmDims& d) {
+  if (!out.has_value())
+    return torch::empty({d.m, d.n}, A.options().dtype(torch::kFloat32));
+  const torch::Tensor& o = *out;
+  K3_CHECK(o.scalar_type() == torch::kFloat32, "out must be float32");
+  K3_CHECK(o.dim() == 2 && o.size(0) == d.m && o.size(1) == d.n,
+           "out must be [M,N]");
+  K3_CHECK(o.is_contiguous(), "out must be contiguous");
+  K3_CHECK(reinterpret_cast<uintptr_t>(o.data_ptr()) % 16 == 0,
+           "out data pointer must be 16-byte aligned");
+  K3_CHECK(o.is_cuda() && o.device() == A.device(),
+           "out must be on the same GPU as A");
+  return o;
 }
 
 }  // namespace
@@ -283,6 +328,86 @@ void mem_verify_fill(torch::Tensor buf, torch::Tensor report,
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+// ---- verified bf16 MFMA GEMM (gemm_kernels.h) ----
+// Like the memtest ops, none of these synchronise with the host.
+
+// `buf` is the stored [rows, cols] bf16 matrix: A[M,K] for which = 0,
+// Bt[N,K] for which = 1 (element [n][k] = gemm_operand(seed, 1, k, n)).
+void gemm_fill(torch::Tensor buf, int64_t which, uint64_t seed, int64_t rows,
+               int64_t cols) {
+  K3_CHECK(which == 0 || which == 1, "which must be 0 (A) or 1 (Bt)");
+  K3_CHECK(buf.scalar_type() == torch::kBFloat16, "buffer must be bfloat16");
+  K3_CHECK(rows > 0 && cols > 0 && cols % 8 == 0 && rows <= (1 << 24) &&
+               cols <= (1 << 24),
+           "rows and cols must be > 0 and cols a multiple of 8");
+  K3_CHECK(buf.numel() == rows * cols, "buffer must hold rows * cols elements");
+  check_mem_buf(buf);
+  k3samd_kern::launch_gemm_fill(at::hip::getCurrentHIPStream(), buf.data_ptr(),
+                                (int)which, seed, rows, cols);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// C[M,N] fp32 = A[M,K] . Bt[N,K]^T on the matrix pipes; any bf16 data.
+// `where` (optional int32 [tiles,2], tile = (m/128)*(N/128) + n/128)
+// receives the XCC_ID and HW_ID registers of each tile's workgroup.
+torch::Tensor gemm_bf16_nt(torch::Tensor A, torch::Tensor Bt,
+                           c10::optional<torch::Tensor> out,
+                           c10::optional<torch::Tensor> where) {
+  GemmDims d = check_gemm_operands(A, Bt);
+  void* where_ptr = nullptr;
+  if (where.has_value()) {
+    const torch::Tensor& w = *where;
+    const int64_t tiles = (d.m / k3samd_kern::kGemmBM) *
+                          (d.n / k3samd_kern::kGemmBN);
+    K3_CHECK(w.scalar_type() == torch::kInt32, "where must be int32");
+    K3_CHECK(w.dim() == 2 && w.size(0) == tiles && w.size(1) == 2 &&
+                 w.is_contiguous(),
+             "where must be a contiguous int32[tiles,2]");
+    K3_CHECK(w.is_cuda() && w.device() == A.device(),
+             "where must be on the same GPU as A");
+    where_ptr = w.data_ptr();
+  }
+  torch::Tensor C = gemm_result(out, A, d);
+  k3samd_kern::launch_gemm_bf16_nt(at::hip::getCurrentHIPStream(),
+                                   A.data_ptr(), Bt.data_ptr(), C.data_ptr(),
+                                   where_ptr, d.m, d.n, d.k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return C;
+}
+
+// The same product in int32 VALU arithmetic (no MFMA), written as fp32.
+// Operands must hold integers in [-128, 127]; K <= 32768 keeps every sum
+// of generator operands exactly representable.
+torch::Tensor gemm_ref_int(torch::Tensor A, torch::Tensor Bt,
+                           c10::optional<torch::Tensor> out) {
+  K3_CHECK(A.dim() != 2 || A.size(1) <= k3samd_kern::kGemmExactMaxK,
+           "gemm_ref_int needs K <= 32768 (exactness bound 256*K <= 2^23)");
+  GemmDims d = check_gemm_operands(A, Bt);
+  torch::Tensor gold = gemm_result(out, A, d);
+  k3samd_kern::launch_gemm_ref_int(at::hip::getCurrentHIPStream(),
+                                   A.data_ptr(), Bt.data_ptr(),
+                                   gold.data_ptr(), d.m, d.n, d.k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return gold;
+}
+
+// Bitwise compare of two equally sized buffers into the memtest report;
+// the report's dword index is the index of the 32-bit element.
+void buf_compare(torch::Tensor buf, torch::Tensor expected,
+                 torch::Tensor report) {
+  K3_CHECK(buf.nbytes() == expected.nbytes(),
+           "buffer and expected must have the same byte size");
+  int64_t n_cells = check_mem_buf(buf);
+  check_mem_buf(expected);
+  K3_CHECK(expected.device() == buf.device(),
+           "expected must be on the same GPU as the buffer");
+  check_mem_report(report, buf);
+  k3samd_kern::launch_buf_compare(at::hip::getCurrentHIPStream(),
+                                  buf.data_ptr(), expected.data_ptr(), n_cells,
+                                  report.data_ptr());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 // Host-side query: the extension only ships gfx950 code objects, so report
 // whether the active device is gfx950.
 bool has_mfma() {
@@ -321,5 +446,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("old_invert"), py::arg("new_pattern"), py::arg("new_seed"),
         py::arg("new_invert"), py::arg("cell_offset") = 0,
         py::arg("nontemporal") = true);
+  m.def("gemm_fill", &gemm_fill, py::arg("buf"), py::arg("which"),
+        py::arg("seed"), py::arg("rows"), py::arg("cols"));
+  m.def("gemm_bf16_nt", &gemm_bf16_nt, py::arg("A"), py::arg("Bt"),
+        py::arg("out") = py::none(), py::arg("where") = py::none());
+  m.def("gemm_ref_int", &gemm_ref_int, py::arg("A"), py::arg("Bt"),
+        py::arg("out") = py::none());
+  m.def("buf_compare", &buf_compare, py::arg("buf"), py::arg("expected"),
+        py::arg("report"));
   m.attr("MEM_REPORT_LEN") = (int64_t)k3samd_kern::kMemReportLen;
 }

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "../../k3samd/ops/hip/gemm_kernels.h"
 #include "../../k3samd/ops/hip/memtest_kernels.h"
 #include "../../k3samd/ops/hip/stream_kernels.h"
 #include "../topology/gpu_health.h"
@@ -366,6 +367,313 @@ int run_memtest(int64_t mib, int vram_percent, int passes, int inject,
   return clean ? 0 : 4;
 }
 
+// ---------------------------------------------------------------------------
+// --gemmtest: verified bf16 MFMA GEMM (kernels in gemm_kernels.h). The
+// operands are small integers, so C is known exactly and compared bitwise
+// against a gold computed without the matrix pipes.
+// Exit codes: 0 clean, 3 self-test / gold spot-check failed, 4 miscompare.
+// ---------------------------------------------------------------------------
+
+// Host-side operand dump (no HIP call): ROWS lines of COLS integers, the
+// logical window gemm_operand(seed, which, ROW0 + i, COL0 + j).
+int gemm_operand_dump(char** a) {
+  const int which = std::atoi(a[0]);
+  const uint64_t seed = std::strtoull(a[1], nullptr, 0);
+  const uint64_t row0 = std::strtoull(a[2], nullptr, 0);
+  const uint64_t col0 = std::strtoull(a[3], nullptr, 0);
+  const uint64_t rows = std::strtoull(a[4], nullptr, 0);
+  const uint64_t cols = std::strtoull(a[5], nullptr, 0);
+  if (which != 0 && which != 1) {
+    std::fprintf(stderr, "mi-stream: operand WHICH must be 0 (A) or 1 (B)\n");
+    return 2;
+  }
+  for (uint64_t i = 0; i < rows; ++i) {
+    for (uint64_t j = 0; j < cols; ++j)
+      std::printf("%s%d", j ? " " : "",
+                  k3samd_kern::gemm_operand(seed, which, (uint32_t)(row0 + i),
+                                            (uint32_t)(col0 + j)));
+    std::printf("\n");
+  }
+  return 0;
+}
+
+// Element (m, n) of the generator product as a host integer dot product.
+long long gemm_host_dot(uint64_t seed, uint32_t m, uint32_t n, int64_t k) {
+  long long s = 0;
+  for (int64_t kk = 0; kk < k; ++kk)
+    s += (long long)k3samd_kern::gemm_operand(seed, 0, m, (uint32_t)kk) *
+         k3samd_kern::gemm_operand(seed, 1, (uint32_t)kk, n);
+  return s;
+}
+
+struct GemmBufs {
+  void *a = nullptr, *bt = nullptr, *c = nullptr, *gold = nullptr;
+  int* where = nullptr;
+  int64_t tiles = 0;
+};
+
+int gemm_alloc(GemmBufs& g, int64_t m, int64_t n, int64_t k) {
+  g.tiles = (m / k3samd_kern::kGemmBM) * (n / k3samd_kern::kGemmBN);
+  HIP_CHECK(hipMalloc(&g.a, (size_t)m * k * 2));
+  HIP_CHECK(hipMalloc(&g.bt, (size_t)n * k * 2));
+  HIP_CHECK(hipMalloc(&g.c, (size_t)m * n * 4));
+  HIP_CHECK(hipMalloc(&g.gold, (size_t)m * n * 4));
+  HIP_CHECK(hipMalloc(&g.where, (size_t)g.tiles * 8));
+  HIP_CHECK(hipMemset(g.c, 0xFF, (size_t)m * n * 4));  // NaN: unwritten != gold
+  HIP_CHECK(hipMemset(g.where, 0xFF, (size_t)g.tiles * 8));
+  return 0;
+}
+
+int gemm_free(GemmBufs& g) {
+  HIP_CHECK(hipFree(g.a));
+  HIP_CHECK(hipFree(g.bt));
+  HIP_CHECK(hipFree(g.c));
+  HIP_CHECK(hipFree(g.gold));
+  HIP_CHECK(hipFree(g.where));
+  return 0;
+}
+
+// Self-test: (1) a 256x256x128 product, both the MFMA result and the
+// integer gold, against the host integer product of gemm_pattern.h;
+// (2) the detector drill of mem_selftest on C: flip three known bits,
+// require exactly those three back. Returns 0 ok, 3 failed, 1 HIP error.
+int gemm_selftest(void* d_report) {
+  using namespace k3samd_kern;
+  const int64_t m = 256, n = 256, k = 128;
+  const uint64_t seed = 0x5EEDF00Dull;
+  GemmBufs g;
+  if (gemm_alloc(g, m, n, k)) return 1;
+  launch_gemm_fill(0, g.a, 0, seed, m, k);
+  launch_gemm_fill(0, g.bt, 1, seed, n, k);
+  launch_gemm_ref_int(0, g.a, g.bt, g.gold, m, n, k);
+  launch_gemm_bf16_nt(0, g.a, g.bt, g.c, g.where, m, n, k);
+  HIP_CHECK(hipGetLastError());
+  std::vector<float> hc(m * n), hg(m * n);
+  HIP_CHECK(hipMemcpy(hc.data(), g.c, hc.size() * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(hg.data(), g.gold, hg.size() * 4, hipMemcpyDeviceToHost));
+  // host operands once, then the integer product
+  std::vector<int> ha(m * k), hb(k * n);
+  for (int64_t i = 0; i < m; ++i)
+    for (int64_t kk = 0; kk < k; ++kk)
+      ha[i * k + kk] = gemm_operand(seed, 0, (uint32_t)i, (uint32_t)kk);
+  for (int64_t kk = 0; kk < k; ++kk)
+    for (int64_t j = 0; j < n; ++j)
+      hb[kk * n + j] = gemm_operand(seed, 1, (uint32_t)kk, (uint32_t)j);
+  long long bad_mfma = 0, bad_gold = 0;
+  for (int64_t i = 0; i < m; ++i)
+    for (int64_t j = 0; j < n; ++j) {
+      int s = 0;
+      for (int64_t kk = 0; kk < k; ++kk) s += ha[i * k + kk] * hb[kk * n + j];
+      if (hc[i * n + j] != (float)s) ++bad_mfma;
+      if (hg[i * n + j] != (float)s) ++bad_gold;
+    }
+  if (bad_mfma || bad_gold) {
+    std::printf("gemmtest selftest: FAIL (256x256x128 vs host product: %lld "
+                "MFMA element(s), %lld gold element(s) differ)\n",
+                bad_mfma, bad_gold);
+    return 3;
+  }
+  std::printf("gemmtest selftest: 256x256x128 MFMA product and integer gold "
+              "match the host product exactly\n");
+
+  const uint64_t e[3] = {0, 12345, (uint64_t)(m * n - 1)};
+  const uint32_t mask[3] = {1u << 0, 1u << 17, 1u << 31};
+  for (int i = 0; i < 3; ++i)
+    if (mem_flip(g.c, e[i], mask[i])) return 1;
+  if (mem_report_reset(d_report)) return 1;
+  launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
+  HIP_CHECK(hipGetLastError());
+  HostMemReport r;
+  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
+  int caught = 0;
+  for (int i = 0; i < 3; ++i) {
+    uint32_t expect;
+    std::memcpy(&expect, &hg[e[i]], 4);
+    for (int s = 0; s < r.n_log(); ++s) {
+      const long long* rec = r.v + kMemReportHeader + 3 * s;
+      if ((uint64_t)rec[0] == e[i] && (uint32_t)rec[1] == expect &&
+          (uint32_t)rec[2] == (expect ^ mask[i])) {
+        ++caught;
+        break;
+      }
+    }
+  }
+  if (gemm_free(g)) return 1;
+  bool ok = caught == 3 && r.bad_dwords() == 3 && r.bad_bits() == 3 &&
+            r.first() == e[0] && r.v[4] == 3 &&
+            r.xor_or() == (mask[0] | mask[1] | mask[2]);
+  if (!ok) {
+    std::printf("gemmtest selftest: FAIL (caught %d/3, bad_elems %lld, "
+                "bad_bits %lld, xor_or 0x%08x)\n",
+                caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
+    return 3;
+  }
+  std::printf("gemmtest selftest: detector caught 3/3 injected flips\n");
+  return 0;
+}
+
+// Element index of injected flip i of `inject` (documented: evenly spaced
+// from element 0, bit i % 32).
+uint64_t gemm_inject_elem(int i, int inject, int64_t m, int64_t n) {
+  return (uint64_t)i * ((uint64_t)(m * n) / (uint64_t)inject);
+}
+
+int run_gemmtest(int64_t m, int64_t n, int64_t k, int iters, int seconds,
+                 int inject, bool do_check) {
+  using namespace k3samd_kern;
+  const uint64_t seed = 0;
+  void* d_report;
+  HIP_CHECK(hipMalloc(&d_report, sizeof(long long) * kMemReportLen));
+  if (do_check) {
+    int rc = gemm_selftest(d_report);
+    if (rc) return rc;
+  }
+  GemmBufs g;
+  if (gemm_alloc(g, m, n, k)) return 1;
+  hipEvent_t ev0, ev1;
+  HIP_CHECK(hipEventCreate(&ev0));
+  HIP_CHECK(hipEventCreate(&ev1));
+  launch_gemm_fill(0, g.a, 0, seed, m, k);
+  launch_gemm_fill(0, g.bt, 1, seed, n, k);
+  HIP_CHECK(hipEventRecord(ev0));
+  launch_gemm_ref_int(0, g.a, g.bt, g.gold, m, n, k);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(ev1));
+  HIP_CHECK(hipEventSynchronize(ev1));
+  float gold_ms;
+  HIP_CHECK(hipEventElapsedTime(&gold_ms, ev0, ev1));
+
+  // gold spot-check: 64 fixed elements against host integer dot products
+  // of the generator — independent of the device entirely
+  for (int i = 0; i < 64; ++i) {
+    const uint32_t row = i == 63 ? (uint32_t)(m - 1)
+                                 : (uint32_t)(((uint64_t)i * 0x9E3779B1ull) % (uint64_t)m);
+    const uint32_t col = i == 63 ? (uint32_t)(n - 1)
+                                 : (uint32_t)(((uint64_t)i * 0x85EBCA6Bull + 7) % (uint64_t)n);
+    float got;
+    HIP_CHECK(hipMemcpy(&got, static_cast<float*>(g.gold) + (size_t)row * n + col,
+                        4, hipMemcpyDeviceToHost));
+    const long long want = gemm_host_dot(seed, row, col, k);
+    if (got != (float)want) {
+      std::printf("gemmtest: gold spot-check FAIL at [%u][%u]: device %.1f, "
+                  "host %lld\n", row, col, got, want);
+      return 3;
+    }
+  }
+  std::printf("gemmtest: %lldx%lldx%lld, gold by integer VALU in %.1f ms, "
+              "spot-check 64/64 vs host%s\n",
+              (long long)m, (long long)n, (long long)k, gold_ms,
+              inject ? " [fault injection ON]" : "");
+
+  int card = -1;  // sysfs sampling, best effort (as --burn)
+  {
+    auto topo = k3samd::enumerate_topology(k3samd::default_sysfs_root());
+    if (!topo.gpus.empty()) card = topo.gpus[0].card_index;
+  }
+  if (mem_report_reset(d_report)) return 1;
+  const double flops_per = 2.0 * (double)m * (double)n * (double)k;
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto since = [&](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double>(now() - t).count();
+  };
+  std::printf("%6s %10s %12s %6s %7s\n", "t(s)", "iters", "TFLOP/s", "temp",
+              "power");
+  long max_temp = -1, max_pw = -1;
+  long long done = 0, done_last = 0;
+  int batch = 1;
+  const auto t0 = now();
+  auto t_last = t0;
+  double next_report = 2.0;
+  auto status = [&] {
+    auto st = k3samd::read_runtime_stats(k3samd::default_sysfs_root(), card);
+    if (st.temp_mc > max_temp) max_temp = st.temp_mc;
+    if (st.power_uw > max_pw) max_pw = st.power_uw;
+    const double dt = since(t_last);
+    std::printf("%6.0f %10lld %12.1f %5ldC %6.0fW\n", since(t0), done,
+                dt > 0 ? (done - done_last) * flops_per / dt / 1e12 : 0.0,
+                st.temp_mc < 0 ? -1 : st.temp_mc / 1000,
+                st.power_uw < 0 ? -1.0 : st.power_uw / 1e6);
+    std::fflush(stdout);
+    done_last = done;
+    t_last = now();
+  };
+  while (seconds > 0 ? since(t0) < (double)seconds : done < iters) {
+    int todo = batch;
+    if (seconds <= 0 && todo > iters - done) todo = (int)(iters - done);
+    const auto tb = now();
+    for (int i = 0; i < todo; ++i) {
+      launch_gemm_bf16_nt(0, g.a, g.bt, g.c, g.where, m, n, k);
+      if (done == 0 && i == 0 && inject > 0) {
+        // operator alerting drill: N single-bit flips at fixed elements of
+        // the first result, before its compare
+        HIP_CHECK(hipDeviceSynchronize());
+        for (int f = 0; f < inject; ++f)
+          if (mem_flip(g.c, gemm_inject_elem(f, inject, m, n), 1u << (f % 32)))
+            return 1;
+      }
+      launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    done += todo;
+    // size the batch to ~0.2 s between host syncs
+    const double per = since(tb) / todo;
+    batch = per > 0 ? (int)(0.2 / per) : 64;
+    if (batch < 1) batch = 1;
+    if (batch > 64) batch = 64;
+    if (since(t0) >= next_report) {
+      status();
+      next_report += 2.0;
+    }
+  }
+  const double total_s = since(t0);
+  if (done != done_last) status();  // the tail since the last line
+
+  HostMemReport r;
+  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
+  std::vector<int> where((size_t)g.tiles * 2);
+  HIP_CHECK(hipMemcpy(where.data(), g.where, where.size() * 4,
+                      hipMemcpyDeviceToHost));
+  auto xcc_of = [&](unsigned long long elem, unsigned* hw_id) {
+    const int64_t row = (int64_t)(elem / (uint64_t)n), col = (int64_t)(elem % (uint64_t)n);
+    const int64_t tile = (row / kGemmBM) * (n / kGemmBN) + col / kGemmBN;
+    if (hw_id) *hw_id = (unsigned)where[2 * tile + 1];
+    return where[2 * tile] & 0xF;
+  };
+  const bool clean = r.bad_dwords() == 0;
+  if (!clean) {
+    std::printf("gemmtest: MISCOMPARE - %lld element(s), %lld bit(s)\n",
+                r.bad_dwords(), r.bad_bits());
+    for (int i = 0; i < r.n_log(); ++i) {
+      const long long* rec = r.v + kMemReportHeader + 3 * i;
+      unsigned hw_id = 0;
+      const int xcc = xcc_of((unsigned long long)rec[0], &hw_id);
+      std::printf("C[%llu][%llu] expected 0x%08x actual 0x%08x xor 0x%08x "
+                  "xcc %d hw_id 0x%08x\n",
+                  (unsigned long long)rec[0] / (unsigned long long)n,
+                  (unsigned long long)rec[0] % (unsigned long long)n,
+                  (unsigned)rec[1], (unsigned)rec[2],
+                  (unsigned)(rec[1] ^ rec[2]), xcc, hw_id);
+    }
+  }
+  std::printf(
+      "{\"payload\": \"mi-gemmtest\", \"m\": %lld, \"n\": %lld, \"k\": %lld, "
+      "\"iters\": %lld, \"bad_elems\": %lld, \"bad_bits\": %lld, "
+      "\"first_bad_row\": %lld, \"first_bad_col\": %lld, "
+      "\"first_bad_xcc\": %d, \"avg_tflops\": %.1f, \"gold_ms\": %.1f, "
+      "\"max_temp_c\": %ld, \"max_power_w\": %.0f, \"compute_clean\": %s}\n",
+      (long long)m, (long long)n, (long long)k, done, r.bad_dwords(),
+      r.bad_bits(), clean ? -1LL : (long long)(r.first() / (uint64_t)n),
+      clean ? -1LL : (long long)(r.first() % (uint64_t)n),
+      clean ? -1 : xcc_of(r.first(), nullptr),
+      done * flops_per / total_s / 1e12, gold_ms,
+      max_temp < 0 ? -1 : max_temp / 1000, max_pw < 0 ? -1.0 : max_pw / 1e6,
+      clean ? "true" : "false");
+  if (gemm_free(g)) return 1;
+  HIP_CHECK(hipFree(d_report));
+  return clean ? 0 : 4;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -380,6 +688,9 @@ int main(int argc, char** argv) {
   int burn_s = 0;
   bool memtest = false;
   int passes = 1, vram_percent = 0, inject = 0;
+  bool gemmtest = false;
+  int64_t gemm_m = 4096, gemm_n = 4096, gemm_k = 4096;
+  int gemm_iters = 0, gemm_seconds = 0, gemm_inject = 0;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mib") && i + 1 < argc)
       mib = std::atoll(argv[++i]);
@@ -409,12 +720,31 @@ int main(int argc, char** argv) {
       inject = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--memtest-pattern-dump") && i + 5 < argc)
       return mem_pattern_dump(argv + i + 1);  // host only: before any HIP call
+    else if (!std::strcmp(argv[i], "--gemmtest"))
+      gemmtest = true;
+    else if (!std::strcmp(argv[i], "--gemm-size") && i + 1 < argc)
+      gemm_m = gemm_n = gemm_k = std::atoll(argv[++i]);
+    else if (!std::strcmp(argv[i], "--gemm-mnk") && i + 3 < argc) {
+      gemm_m = std::atoll(argv[++i]);
+      gemm_n = std::atoll(argv[++i]);
+      gemm_k = std::atoll(argv[++i]);
+    } else if (!std::strcmp(argv[i], "--gemm-iters") && i + 1 < argc)
+      gemm_iters = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--gemm-seconds") && i + 1 < argc)
+      gemm_seconds = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--gemm-inject") && i + 1 < argc)
+      gemm_inject = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--gemm-operand-dump") && i + 6 < argc)
+      return gemm_operand_dump(argv + i + 1);  // host only: before any HIP call
     else {
       std::printf("mi-stream [--mib N] [--iters N] [--device D] [--no-mfma]"
                   " [--tune] [--lds-compare] [--all-gpus] [--burn SECONDS]"
                   " [--memtest [--passes N] [--vram-percent P]"
                   " [--memtest-inject N]] [--memtest-pattern-dump PATTERN"
-                  " SEED INVERT CELL_OFFSET N_CELLS]\n");
+                  " SEED INVERT CELL_OFFSET N_CELLS]"
+                  " [--gemmtest [--gemm-size S | --gemm-mnk M N K]"
+                  " [--gemm-iters I | --gemm-seconds T] [--gemm-inject N]]"
+                  " [--gemm-operand-dump WHICH SEED ROW0 COL0 ROWS COLS]\n");
       return !std::strcmp(argv[i], "--help") ? 0 : 2;
     }
   }
@@ -425,6 +755,20 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "mi-stream: --memtest needs --passes >= 1, --mib >= 1,"
                          " --vram-percent 1..90, --memtest-inject 1..16\n");
     return 2;
+  }
+
+  if (gemmtest) {
+    if (gemm_iters == 0 && gemm_seconds == 0) gemm_seconds = 1;  // default
+    if (!k3samd_kern::gemm_shape_ok(gemm_m, gemm_n, gemm_k) ||
+        gemm_k > k3samd_kern::kGemmExactMaxK || gemm_iters < 0 ||
+        gemm_seconds < 0 || (gemm_iters > 0 && gemm_seconds > 0) ||
+        gemm_inject < 0 || gemm_inject > 16) {
+      std::fprintf(stderr, "mi-stream: --gemmtest needs M and N multiples of"
+                           " 128, K a multiple of 64 and <= 32768, one of"
+                           " --gemm-iters >= 1 / --gemm-seconds >= 1,"
+                           " --gemm-inject 1..16\n");
+      return 2;
+    }
   }
 
   int ndev = 0;
@@ -501,8 +845,12 @@ int main(int argc, char** argv) {
               gpu_name, prop.gcnArchName, ndev, prop.multiProcessorCount,
               (double)prop.totalGlobalMem / (1 << 30));
 
-  // exit 3: an oracle/self-test failed; exit 4: memtest data miscompare
+  // exit 3: an oracle/self-test failed; exit 4: memtest or gemmtest data
+  // miscompare
   if (memtest) return run_memtest(mib, vram_percent, passes, inject, do_check);
+  if (gemmtest)
+    return run_gemmtest(gemm_m, gemm_n, gemm_k, gemm_iters, gemm_seconds,
+                        gemm_inject, do_check);
 
   if (do_check && !self_check()) return 3;  // pod log is the oracle
 
