@@ -36,11 +36,8 @@ def _needs_rebuild() -> bool:
     if not so.exists():
         return True
     so_mtime = so.stat().st_mtime
-    hip_dir = HIP_SRC.parent
-    deps = [HIP_SRC, hip_dir / "stream_kernels.h",
-            hip_dir / "memtest_kernels.h", hip_dir / "memtest_pattern.h",
-            hip_dir / "gemm_kernels.h", hip_dir / "gemm_pattern.h"]
-    return any(d.exists() and d.stat().st_mtime > so_mtime for d in deps)
+    deps = [HIP_SRC, *HIP_SRC.parent.glob("*.h")]
+    return any(d.stat().st_mtime > so_mtime for d in deps)
 
 
 def build_extension(verbose: bool = True) -> Path:

@@ -15,8 +15,6 @@
 namespace {
 
 using k3samd_kern::f4;
-using k3samd_kern::kThreadsPerBlock;
-using k3samd_kern::stream_grid;
 
 #define K3_CHECK(cond, msg) TORCH_CHECK(cond, "k3samd: ", msg)
 
@@ -25,6 +23,11 @@ void check_stream_args(const torch::Tensor& t) {
   K3_CHECK(t.scalar_type() == torch::kFloat32, "tensor must be float32");
   K3_CHECK(t.is_contiguous(), "tensor must be contiguous");
   K3_CHECK(t.numel() % 4 == 0, "numel must be divisible by 4");
+}
+
+// float4 view of a tensor that passed check_stream_args
+f4* f4_ptr(const torch::Tensor& t) {
+  return reinterpret_cast<f4*>(t.data_ptr<float>());
 }
 
 // Memory-test target: any contiguous GPU tensor, any dtype, whole 16-byte
@@ -108,22 +111,9 @@ void stream_triad(torch::Tensor a, torch::Tensor b, torch::Tensor c, double s,
   check_stream_args(b);
   check_stream_args(c);
   K3_CHECK(a.numel() == b.numel() && a.numel() == c.numel(), "size mismatch");
-  int64_t n4 = a.numel() / 4;
-  auto stream = at::hip::getCurrentHIPStream();
-  auto* ap = reinterpret_cast<f4*>(a.data_ptr<float>());
-  auto* bp = reinterpret_cast<const f4*>(b.data_ptr<float>());
-  auto* cp = reinterpret_cast<const f4*>(c.data_ptr<float>());
-  k3samd_kern::launch_chunked(n4, [&](int64_t off, int64_t cnt) {
-    if (nontemporal) {
-      hipLaunchKernelGGL(k3samd_kern::stream_triad_kernel<true>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, bp + off, cp + off, (float)s, cnt);
-    } else {
-      hipLaunchKernelGGL(k3samd_kern::stream_triad_kernel<false>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, bp + off, cp + off, (float)s, cnt);
-    }
-  });
+  k3samd_kern::launch_stream_triad(at::hip::getCurrentHIPStream(), f4_ptr(a),
+                                   f4_ptr(b), f4_ptr(c), (float)s,
+                                   a.numel() / 4, nontemporal);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -131,21 +121,8 @@ void stream_copy(torch::Tensor a, torch::Tensor b, bool nontemporal) {
   check_stream_args(a);
   check_stream_args(b);
   K3_CHECK(a.numel() == b.numel(), "size mismatch");
-  int64_t n4 = a.numel() / 4;
-  auto stream = at::hip::getCurrentHIPStream();
-  auto* ap = reinterpret_cast<f4*>(a.data_ptr<float>());
-  auto* bp = reinterpret_cast<const f4*>(b.data_ptr<float>());
-  k3samd_kern::launch_chunked(n4, [&](int64_t off, int64_t cnt) {
-    if (nontemporal) {
-      hipLaunchKernelGGL(k3samd_kern::stream_copy_kernel<true>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, bp + off, cnt);
-    } else {
-      hipLaunchKernelGGL(k3samd_kern::stream_copy_kernel<false>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, bp + off, cnt);
-    }
-  });
+  k3samd_kern::launch_stream_copy(at::hip::getCurrentHIPStream(), f4_ptr(a),
+                                  f4_ptr(b), a.numel() / 4, nontemporal);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -153,21 +130,9 @@ void stream_scale(torch::Tensor a, torch::Tensor c, double s, bool nontemporal) 
   check_stream_args(a);
   check_stream_args(c);
   K3_CHECK(a.numel() == c.numel(), "size mismatch");
-  int64_t n4 = a.numel() / 4;
-  auto stream = at::hip::getCurrentHIPStream();
-  auto* ap = reinterpret_cast<f4*>(a.data_ptr<float>());
-  auto* cp = reinterpret_cast<const f4*>(c.data_ptr<float>());
-  k3samd_kern::launch_chunked(n4, [&](int64_t off, int64_t cnt) {
-    if (nontemporal) {
-      hipLaunchKernelGGL(k3samd_kern::stream_scale_kernel<true>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, cp + off, (float)s, cnt);
-    } else {
-      hipLaunchKernelGGL(k3samd_kern::stream_scale_kernel<false>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, cp + off, (float)s, cnt);
-    }
-  });
+  k3samd_kern::launch_stream_scale(at::hip::getCurrentHIPStream(), f4_ptr(a),
+                                   f4_ptr(c), (float)s, a.numel() / 4,
+                                   nontemporal);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -177,22 +142,9 @@ void stream_add(torch::Tensor a, torch::Tensor b, torch::Tensor c,
   check_stream_args(b);
   check_stream_args(c);
   K3_CHECK(a.numel() == b.numel() && a.numel() == c.numel(), "size mismatch");
-  int64_t n4 = a.numel() / 4;
-  auto stream = at::hip::getCurrentHIPStream();
-  auto* ap = reinterpret_cast<f4*>(a.data_ptr<float>());
-  auto* bp = reinterpret_cast<const f4*>(b.data_ptr<float>());
-  auto* cp = reinterpret_cast<const f4*>(c.data_ptr<float>());
-  k3samd_kern::launch_chunked(n4, [&](int64_t off, int64_t cnt) {
-    if (nontemporal) {
-      hipLaunchKernelGGL(k3samd_kern::stream_add_kernel<true>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, bp + off, cp + off, cnt);
-    } else {
-      hipLaunchKernelGGL(k3samd_kern::stream_add_kernel<false>,
-                         dim3(stream_grid(cnt)), dim3(kThreadsPerBlock), 0,
-                         stream, ap + off, bp + off, cp + off, cnt);
-    }
-  });
+  k3samd_kern::launch_stream_add(at::hip::getCurrentHIPStream(), f4_ptr(a),
+                                 f4_ptr(b), f4_ptr(c), a.numel() / 4,
+                                 nontemporal);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -206,32 +158,12 @@ double mfma_throughput(torch::Tensor out, int64_t iters, int64_t shape) {
            "shape must be 16, 32 (bf16), 8 (MX-fp8) or 4 (MX-fp4)");
   int64_t blocks = out.numel();
   K3_CHECK(blocks > 0 && blocks <= (1 << 22), "bad block count");
-  auto stream = at::hip::getCurrentHIPStream();
-  // shape 16: 4 chains x 16384 FLOP per iter; shape 32: 4 chains x 2
-  // unroll per i+=2 step = 4 MFMAs/iter x 32768 FLOP
-  double flops_per_wave_iter = shape == 32 ? 4.0 * 32768.0 : 4.0 * 16384.0;
-  if (shape == 16) {
-    hipLaunchKernelGGL(k3samd_kern::mfma_throughput_kernel, dim3(blocks),
-                       dim3(kThreadsPerBlock), 0, stream,
-                       out.data_ptr<float>(), (int)iters);
-  } else if (shape == 32) {
-    hipLaunchKernelGGL(k3samd_kern::mfma_throughput32_kernel, dim3(blocks),
-                       dim3(kThreadsPerBlock), 0, stream,
-                       out.data_ptr<float>(), (int)iters);
-  } else {
-    flops_per_wave_iter = 4.0 * 65536.0;  // K=128 MX shapes
-    if (shape == 8) {
-      hipLaunchKernelGGL(k3samd_kern::mfma_throughput_mx_kernel<0>,
-                         dim3(blocks), dim3(kThreadsPerBlock), 0, stream,
-                         out.data_ptr<float>(), (int)iters);
-    } else {
-      hipLaunchKernelGGL(k3samd_kern::mfma_throughput_mx_kernel<4>,
-                         dim3(blocks), dim3(kThreadsPerBlock), 0, stream,
-                         out.data_ptr<float>(), (int)iters);
-    }
-  }
+  const auto kind = static_cast<k3samd_kern::MfmaKind>(shape);
+  k3samd_kern::launch_mfma_throughput(at::hip::getCurrentHIPStream(), kind,
+                                      out.data_ptr<float>(), (int)blocks,
+                                      (int)iters);
   C10_HIP_KERNEL_LAUNCH_CHECK();
-  return (double)blocks * 4.0 * flops_per_wave_iter * (double)iters;
+  return k3samd_kern::mfma_throughput_flops(kind, blocks, iters);
 }
 
 torch::Tensor mfma_gemm16(torch::Tensor A, torch::Tensor B, int64_t layout) {
@@ -272,19 +204,12 @@ torch::Tensor mx_gemm16(torch::Tensor A, torch::Tensor B, int64_t fmt) {
            "A must be [16,KB], B [16,KB] (B column-major-packed)");
   auto D = torch::empty({16, 16}, A.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStream();
-  if (fmt == 0) {
-    hipLaunchKernelGGL(k3samd_kern::mx_gemm16_kernel<0>, dim3(1), dim3(64),
-                       0, stream,
-                       reinterpret_cast<const uint8_t*>(A.data_ptr()),
-                       reinterpret_cast<const uint8_t*>(B.data_ptr()),
-                       D.data_ptr<float>());
-  } else {
-    hipLaunchKernelGGL(k3samd_kern::mx_gemm16_kernel<4>, dim3(1), dim3(64),
-                       0, stream,
-                       reinterpret_cast<const uint8_t*>(A.data_ptr()),
-                       reinterpret_cast<const uint8_t*>(B.data_ptr()),
-                       D.data_ptr<float>());
-  }
+  auto kernel = fmt == 0 ? k3samd_kern::mx_gemm16_kernel<0>
+                         : k3samd_kern::mx_gemm16_kernel<4>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, stream,
+                     reinterpret_cast<const uint8_t*>(A.data_ptr()),
+                     reinterpret_cast<const uint8_t*>(B.data_ptr()),
+                     D.data_ptr<float>());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return D;
 }

@@ -1,6 +1,8 @@
-// CDNA4 (gfx950) device kernels shared by the torch extension
-// (k3samd_kernels.hip) and the standalone in-pod smoke binary
-// (native/hipsmoke/mi_stream.hip). Pure HIP — no torch dependency.
+// CDNA4 (gfx950) device kernels and their host-side launch_* helpers,
+// shared by the torch extension (k3samd_kernels.hip) and the standalone
+// in-pod smoke binary (native/hipsmoke/mi_stream.hip); both launch the
+// STREAM and MFMA-throughput kernels only through the helpers at the end
+// of this file. Pure HIP — no torch dependency.
 //
 // Design (MI355X-first):
 //  * 16 B/lane (float4 ext-vector) loads/stores — 1 KiB per wave64 vector
@@ -374,6 +376,94 @@ inline void launch_chunked(int64_t n4, LaunchOne&& launch_one) {
     launch_one(off, count);
     off += count;
   } while (off < n4);
+}
+
+// ---- host-side launchers (chunked; no sync, errors via hipGetLastError) ----
+// launch_stream is the one place that forms the flat grid, stream_grid(cnt)
+// blocks x kThreadsPerBlock per chunk; the wrappers below are the one place
+// where `nt` picks the <true>/<false> instantiation.
+
+template <typename T>
+inline T* chunk_arg(T* p, int64_t off) { return p + off; }
+inline float chunk_arg(float s, int64_t) { return s; }
+
+// kernel(args..., n4) over n4 float4s; pointer args advance with the chunk
+template <typename Kernel, typename... Args>
+inline void launch_stream(hipStream_t stream, Kernel kernel, int64_t n4,
+                          Args... args) {
+  launch_chunked(n4, [&](int64_t off, int64_t cnt) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)stream_grid(cnt)),
+                       dim3(kThreadsPerBlock), 0, stream,
+                       chunk_arg(args, off)..., cnt);
+  });
+}
+
+inline void launch_stream_copy(hipStream_t stream, f4* a, const f4* b,
+                               int64_t n4, bool nt) {
+  auto kernel = nt ? stream_copy_kernel<true> : stream_copy_kernel<false>;
+  launch_stream(stream, kernel, n4, a, b);
+}
+inline void launch_stream_scale(hipStream_t stream, f4* a, const f4* c,
+                                float s, int64_t n4, bool nt) {
+  auto kernel = nt ? stream_scale_kernel<true> : stream_scale_kernel<false>;
+  launch_stream(stream, kernel, n4, a, c, s);
+}
+inline void launch_stream_add(hipStream_t stream, f4* a, const f4* b,
+                              const f4* c, int64_t n4, bool nt) {
+  auto kernel = nt ? stream_add_kernel<true> : stream_add_kernel<false>;
+  launch_stream(stream, kernel, n4, a, b, c);
+}
+inline void launch_stream_triad(hipStream_t stream, f4* a, const f4* b,
+                                const f4* c, float s, int64_t n4, bool nt) {
+  auto kernel = nt ? stream_triad_kernel<true> : stream_triad_kernel<false>;
+  launch_stream(stream, kernel, n4, a, b, c, s);
+}
+inline void launch_stream_triad_lds(hipStream_t stream, f4* a, const f4* b,
+                                    const f4* c, float s, int64_t n4) {
+  launch_stream(stream, stream_triad_lds_kernel, n4, a, b, c, s);
+}
+
+// The MFMA throughput kernels, numbered by the torch binding's `shape`.
+enum MfmaKind {
+  kMfmaBf16_16x16x32 = 16,  // mfma_throughput_kernel
+  kMfmaBf16_32x32x16 = 32,  // mfma_throughput32_kernel
+  kMfmaMxFp8 = 8,           // mfma_throughput_mx_kernel<0>
+  kMfmaMxFp6 = 6,           // mfma_throughput_mx_kernel<2>
+  kMfmaMxFp4 = 4,           // mfma_throughput_mx_kernel<4>
+};
+
+// FLOPs of one launch: `blocks` blocks of kThreadsPerBlock / 64 waves, 4
+// chains per wave. The 16x16 kernels issue one MFMA per chain per
+// iteration; the 32x32 kernel issues 8 (4 chains, 2 deep) per `i += 2`.
+constexpr double mfma_throughput_flops(MfmaKind kind, int64_t blocks,
+                                       int64_t iters) {
+  const double flop_per_mfma = kind == kMfmaBf16_16x16x32   ? 16384.0
+                               : kind == kMfmaBf16_32x32x16 ? 32768.0
+                                                            : 65536.0;
+  const double mfma_per_iter = kind == kMfmaBf16_32x32x16 ? 8.0 / 2 : 4.0;
+  return (double)blocks * (kThreadsPerBlock / 64) * mfma_per_iter *
+         flop_per_mfma * (double)iters;
+}
+// the values of the hand-written formulas this replaced: mi-stream's
+// table, its --burn, and the torch binding (shape 32 and MX)
+static_assert(mfma_throughput_flops(kMfmaBf16_16x16x32, 4096, 4096) ==
+              4096.0 * 4 * 4 * 16384.0 * 4096);
+static_assert(mfma_throughput_flops(kMfmaBf16_16x16x32, 1024, 512) ==
+              1024 * 4.0 * 4.0 * 16384.0 * 512.0);
+static_assert(mfma_throughput_flops(kMfmaBf16_32x32x16, 1000, 300) ==
+              1000.0 * 4.0 * (4.0 * 32768.0) * 300.0);
+static_assert(mfma_throughput_flops(kMfmaMxFp4, 1000, 300) ==
+              1000.0 * 4.0 * (4.0 * 65536.0) * 300.0);
+
+inline void launch_mfma_throughput(hipStream_t stream, MfmaKind kind,
+                                   float* out, int blocks, int iters) {
+  auto kernel = kind == kMfmaBf16_16x16x32   ? mfma_throughput_kernel
+                : kind == kMfmaBf16_32x32x16 ? mfma_throughput32_kernel
+                : kind == kMfmaMxFp8         ? mfma_throughput_mx_kernel<0>
+                : kind == kMfmaMxFp6         ? mfma_throughput_mx_kernel<2>
+                                             : mfma_throughput_mx_kernel<4>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kThreadsPerBlock), 0, stream,
+                     out, iters);
 }
 
 }  // namespace k3samd_kern

@@ -9,13 +9,19 @@
 // machine-readable JSON line. No torch dependency — links only the HIP
 // runtime, so the smoke container stays small.
 //
+// Layout: the pieces the modes share, then one run_* function per mode;
+// main() parses, validates and dispatches. The kernels and their launch_*
+// helpers live in k3samd/ops/hip/*.h.
+//
 // Build: hipcc --offload-arch=gfx950 -O3 mi_stream.hip -o mi-stream
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../k3samd/ops/hip/gemm_kernels.h"
@@ -38,134 +44,87 @@ using k3samd_kern::f4;
 
 namespace {
 
-struct Timing {
-  float best_ms = 1e30f;
-};
+// ---- pieces the modes share ----
+
+constexpr float kScalar = 2.5f;  // the s of scale and triad
 
 double gbps(double bytes, float ms) { return bytes / (ms * 1e6); }
+double tflops(double flops, float ms) { return flops / (ms * 1e9); }
 
-// Numerics self-check: the pod log doubles as a correctness oracle (the
-// reference's nvidia-smi output carried version oracles the same way,
-// /root/reference/README.md:139-147). Three checks against host-computed
-// references: fp32 triad (exact), one bf16 MFMA tile, one block-scaled
-// MX-fp8 tile (identity-A => must reproduce B exactly).
-bool self_check() {
-  using namespace k3samd_kern;
-  bool ok = true;
-  // --- triad, 4096 elements, exactly-representable values
-  {
-    const int64_t n = 4096, n4 = n / 4;
-    float *a, *b, *c;
-    (void)hipMalloc(&a, n * 4);
-    (void)hipMalloc(&b, n * 4);
-    (void)hipMalloc(&c, n * 4);
-    std::vector<float> hb(n), hc(n), ha(n);
-    for (int64_t i = 0; i < n; ++i) {
-      hb[i] = (float)((i % 31) - 15);
-      hc[i] = (float)((i % 17) - 8) * 0.5f;
-    }
-    (void)hipMemcpy(b, hb.data(), n * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(c, hc.data(), n * 4, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(stream_triad_kernel<true>, dim3(stream_grid(n4)),
-                       dim3(kThreadsPerBlock), 0, 0, (f4*)a, (f4*)b, (f4*)c,
-                       2.5f, n4);
-    (void)hipMemcpy(ha.data(), a, n * 4, hipMemcpyDeviceToHost);
-    for (int64_t i = 0; i < n && ok; ++i)
-      if (ha[i] != hb[i] + 2.5f * hc[i]) ok = false;
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(c);
-    if (!ok) { std::printf("numerics: triad FAIL\n"); return false; }
-  }
-#if 1
-  // --- bf16 MFMA tile vs host float reference
-  double mfma_err = 0;
-  {
-    uint16_t *A, *B; float* D;
-    (void)hipMalloc(&A, 16 * 32 * 2);
-    (void)hipMalloc(&B, 32 * 16 * 2);
-    (void)hipMalloc(&D, 16 * 16 * 4);
-    std::vector<uint16_t> hA(16 * 32), hB(32 * 16);
-    std::vector<float> fA(16 * 32), fB(32 * 16);
-    auto to_bf16 = [](float f) -> uint16_t {
-      uint32_t u;
-      std::memcpy(&u, &f, 4);
-      return (uint16_t)(u >> 16);  // values chosen exactly representable
-    };
-    for (int i = 0; i < 16 * 32; ++i) {
-      fA[i] = (float)((i % 13) - 6) * 0.25f;
-      hA[i] = to_bf16(fA[i]);
-    }
-    for (int i = 0; i < 32 * 16; ++i) {
-      fB[i] = (float)((i % 11) - 5) * 0.5f;   // asymmetric vs A
-      hB[i] = to_bf16(fB[i]);
-    }
-    (void)hipMemcpy(A, hA.data(), hA.size() * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(B, hB.data(), hB.size() * 2, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(mfma_gemm16_kernel, dim3(1), dim3(64), 0, 0, A, B, D,
-                       0);
-    std::vector<float> hD(256);
-    (void)hipMemcpy(hD.data(), D, 256 * 4, hipMemcpyDeviceToHost);
-    for (int i = 0; i < 16; ++i)
-      for (int j = 0; j < 16; ++j) {
-        float ref = 0;
-        for (int k = 0; k < 32; ++k) ref += fA[i * 32 + k] * fB[k * 16 + j];
-        double e = std::abs(hD[i * 16 + j] - ref);
-        if (e > mfma_err) mfma_err = e;
-      }
-    (void)hipFree(A); (void)hipFree(B); (void)hipFree(D);
-    if (mfma_err > 1e-3) {
-      std::printf("numerics: bf16 MFMA FAIL (err %g)\n", mfma_err);
-      return false;
-    }
-  }
-  // --- MX-fp8 identity tile: D must equal B rows exactly
-  double mx_err = 0;
-  {
-    uint8_t *A, *B; float* D;
-    (void)hipMalloc(&A, 16 * 128);
-    (void)hipMalloc(&B, 16 * 128);
-    (void)hipMalloc(&D, 16 * 16 * 4);
-    std::vector<uint8_t> hA(16 * 128, 0), hB(16 * 128);
-    for (int i = 0; i < 16; ++i) hA[i * 128 + i] = 0x38;  // e4m3 1.0 on diag
-    // B values: exact small e4m3 codes, col-major pack, asymmetric
-    std::vector<float> fB(128 * 16);
-    const float lut[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
-    for (int k = 0; k < 128; ++k)
-      for (int j = 0; j < 16; ++j) {
-        int code = (k * 7 + j * 3) % 16;  // uses sign bit too
-        float v = lut[code & 7] * ((code & 8) ? -1.f : 1.f);
-        fB[k * 16 + j] = v;
-        // e4m3 encodings of the lut: 0,0x30,0x38,0x3c,0x40,0x44,0x48,0x4c
-        const uint8_t enc[8] = {0, 0x30, 0x38, 0x3c, 0x40, 0x44, 0x48, 0x4c};
-        hB[j * 128 + k] = enc[code & 7] | ((code & 8) ? 0x80 : 0);
-      }
-    (void)hipMemcpy(A, hA.data(), hA.size(), hipMemcpyHostToDevice);
-    (void)hipMemcpy(B, hB.data(), hB.size(), hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(mx_gemm16_kernel<0>, dim3(1), dim3(64), 0, 0, A, B, D);
-    std::vector<float> hD(256);
-    (void)hipMemcpy(hD.data(), D, 256 * 4, hipMemcpyDeviceToHost);
-    for (int i = 0; i < 16; ++i)
-      for (int j = 0; j < 16; ++j) {
-        double e = std::abs(hD[i * 16 + j] - fB[i * 16 + j]);
-        if (e > mx_err) mx_err = e;
-      }
-    (void)hipFree(A); (void)hipFree(B); (void)hipFree(D);
-    if (mx_err != 0.0) {
-      std::printf("numerics: MX-fp8 FAIL (err %g)\n", mx_err);
-      return false;
-    }
-  }
-  std::printf(
-      "numerics: triad exact, bf16 MFMA err %.2g, MX-fp8 identity exact\n",
-      mfma_err);
-#endif
-  return true;
+using Clock = std::chrono::steady_clock;
+double seconds_since(Clock::time_point t) {
+  return std::chrono::duration<double>(Clock::now() - t).count();
 }
 
-// ---------------------------------------------------------------------------
-// --memtest: HBM pattern memory test (kernels in memtest_kernels.h).
-// Exit codes: 0 clean, 3 detector self-test failed, 4 data miscompare.
-// ---------------------------------------------------------------------------
+// Owning device allocation: move-only (the move constructor deletes the
+// copies), freed by the destructor, so every early return releases it.
+template <typename T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+  ~DevBuf() { (void)hipFree(p_); }  // hipFree(nullptr) is a no-op
+  hipError_t alloc(size_t bytes) { return hipMalloc((void**)&p_, bytes); }
+  operator T*() const { return p_; }
 
+ private:
+  T* p_ = nullptr;
+};
+
+// "Warm up, then best of N between two events" on the null stream: `warm`
+// untimed calls of launch(true) and a device sync, then the smallest time
+// of `reps` calls of launch(false). The counts decide what a printed rate
+// means, so each call site states its own.
+struct EventTimer {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;  // created on first use
+
+  template <typename Launch>
+  int best_of(int warm, int reps, Launch&& launch, float* best_ms) {
+    if (!ev0) {
+      HIP_CHECK(hipEventCreate(&ev0));
+      HIP_CHECK(hipEventCreate(&ev1));
+    }
+    for (int w = 0; w < warm; ++w) launch(true);
+    HIP_CHECK(hipDeviceSynchronize());
+    *best_ms = 1e30f;
+    for (int rep = 0; rep < reps; ++rep) {
+      float ms;
+      HIP_CHECK(hipEventRecord(ev0));
+      launch(false);
+      HIP_CHECK(hipEventRecord(ev1));
+      HIP_CHECK(hipEventSynchronize(ev1));
+      HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+      if (ms < *best_ms) *best_ms = ms;
+    }
+    HIP_CHECK(hipGetLastError());
+    return 0;
+  }
+};
+
+// Best-effort temperature/power sampling of the first GPU from sysfs; a
+// field the box does not expose reads -1.
+struct ThermalSampler {
+  int card = -1;
+  long max_temp_c = -1;
+  double max_power_w = -1.0;
+  char cells[32] = "";  // "temp power" of the last sample, for a status line
+
+  ThermalSampler() {
+    auto topo = k3samd::enumerate_topology(k3samd::default_sysfs_root());
+    if (!topo.gpus.empty()) card = topo.gpus[0].card_index;
+  }
+  k3samd::GpuRuntimeStats sample() {
+    auto st = k3samd::read_runtime_stats(k3samd::default_sysfs_root(), card);
+    const long temp_c = st.temp_mc < 0 ? -1 : st.temp_mc / 1000;
+    const double power_w = st.power_uw < 0 ? -1.0 : st.power_uw / 1e6;
+    if (temp_c > max_temp_c) max_temp_c = temp_c;
+    if (power_w > max_power_w) max_power_w = power_w;
+    std::snprintf(cells, sizeof(cells), "%5ldC %6.0fW", temp_c, power_w);
+    return st;
+  }
+};
+
+// Host copy of the device report that mem_verify*/buf_compare accumulate.
 struct HostMemReport {
   long long v[k3samd_kern::kMemReportLen];
   long long bad_dwords() const { return v[0]; }
@@ -173,8 +132,11 @@ struct HostMemReport {
   unsigned long long first() const { return (unsigned long long)v[2]; }
   unsigned xor_or() const { return (unsigned)v[3]; }
   int n_log() const {
-    return v[4] > k3samd_kern::kMemLogSlots ? k3samd_kern::kMemLogSlots
-                                            : (int)v[4];
+    return (int)std::min<long long>(v[4], k3samd_kern::kMemLogSlots);
+  }
+  // log record i: {dword or element index, expected, actual}
+  const long long* log(int i) const {
+    return v + k3samd_kern::kMemReportHeader + 3 * i;
   }
 };
 
@@ -195,44 +157,188 @@ int mem_flip(void* buf, uint64_t g, uint32_t mask) {
   return 0;
 }
 
-// Detector self-test: a detector that has never fired proves nothing.
-// Fill 1 MiB, flip three known bits, verify, and require exactly those
-// three dwords/bits (count, first index, xor-or and log) to come back.
+// Detector drill of the memtest and gemmtest self-tests: a detector that
+// has never fired proves nothing, so each flips three known bits and
+// requires exactly those three back, by count, first index, xor-or and
+// log. `index` ascends; `expect` is the dword before the flip.
+struct DrillFlip {
+  uint64_t index;
+  uint32_t expect, mask;
+};
+
+bool drill_passed(const HostMemReport& r, const DrillFlip (&flips)[3],
+                  int* caught) {
+  *caught = 0;
+  for (const DrillFlip& f : flips)
+    for (int s = 0; s < r.n_log(); ++s) {
+      const long long* rec = r.log(s);
+      if ((uint64_t)rec[0] == f.index && (uint32_t)rec[1] == f.expect &&
+          (uint32_t)rec[2] == (f.expect ^ f.mask)) {
+        ++*caught;
+        break;
+      }
+    }
+  return *caught == 3 && r.bad_dwords() == 3 && r.bad_bits() == 3 &&
+         r.first() == flips[0].index && r.v[4] == 3 &&
+         r.xor_or() == (flips[0].mask | flips[1].mask | flips[2].mask);
+}
+
+struct Options {
+  int64_t mib = 1024;
+  int iters = 20, device = 0;
+  bool do_mfma = true, do_check = true;
+  bool all_gpus = false, lds_compare = false, tune = false;
+  int burn_s = 0;
+  bool memtest = false;
+  int passes = 1, vram_percent = 0, inject = 0;
+  bool gemmtest = false;
+  int64_t gemm_m = 4096, gemm_n = 4096, gemm_k = 4096;
+  int gemm_iters = 0, gemm_seconds = 0, gemm_inject = 0;
+};
+
+// Numerics self-check: the pod log doubles as a correctness oracle (the
+// reference's nvidia-smi output carried version oracles the same way,
+// /root/reference/README.md:139-147). Three checks against host-computed
+// references: fp32 triad (exact), one bf16 MFMA tile, one block-scaled
+// MX-fp8 tile (identity-A => must reproduce B exactly).
+bool self_check() {
+  using namespace k3samd_kern;
+  // --- triad, 4096 elements, exactly-representable values
+  {
+    const int64_t n = 4096, n4 = n / 4;
+    DevBuf<f4> a, b, c;
+    (void)a.alloc(n * 4);
+    (void)b.alloc(n * 4);
+    (void)c.alloc(n * 4);
+    std::vector<float> hb(n), hc(n), ha(n);
+    for (int64_t i = 0; i < n; ++i) {
+      hb[i] = (float)((i % 31) - 15);
+      hc[i] = (float)((i % 17) - 8) * 0.5f;
+    }
+    (void)hipMemcpy(b, hb.data(), n * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(c, hc.data(), n * 4, hipMemcpyHostToDevice);
+    launch_stream_triad(0, a, b, c, kScalar, n4, true);
+    (void)hipMemcpy(ha.data(), a, n * 4, hipMemcpyDeviceToHost);
+    for (int64_t i = 0; i < n; ++i)
+      if (ha[i] != hb[i] + kScalar * hc[i]) {
+        std::printf("numerics: triad FAIL\n");
+        return false;
+      }
+  }
+  // --- bf16 MFMA tile vs host float reference
+  double mfma_err = 0;
+  {
+    DevBuf<uint16_t> A, B;
+    DevBuf<float> D;
+    (void)A.alloc(16 * 32 * 2);
+    (void)B.alloc(32 * 16 * 2);
+    (void)D.alloc(16 * 16 * 4);
+    std::vector<uint16_t> hA(16 * 32), hB(32 * 16);
+    std::vector<float> fA(16 * 32), fB(32 * 16);
+    auto to_bf16 = [](float f) -> uint16_t {
+      uint32_t u;
+      std::memcpy(&u, &f, 4);
+      return (uint16_t)(u >> 16);  // values chosen exactly representable
+    };
+    for (int i = 0; i < 16 * 32; ++i) {
+      fA[i] = (float)((i % 13) - 6) * 0.25f;
+      hA[i] = to_bf16(fA[i]);
+    }
+    for (int i = 0; i < 32 * 16; ++i) {
+      fB[i] = (float)((i % 11) - 5) * 0.5f;   // asymmetric vs A
+      hB[i] = to_bf16(fB[i]);
+    }
+    (void)hipMemcpy(A, hA.data(), hA.size() * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(B, hB.data(), hB.size() * 2, hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(mfma_gemm16_kernel, dim3(1), dim3(64), 0, 0,
+                       (const uint16_t*)A, (const uint16_t*)B, (float*)D, 0);
+    std::vector<float> hD(256);
+    (void)hipMemcpy(hD.data(), D, 256 * 4, hipMemcpyDeviceToHost);
+    for (int i = 0; i < 16; ++i)
+      for (int j = 0; j < 16; ++j) {
+        float ref = 0;
+        for (int k = 0; k < 32; ++k) ref += fA[i * 32 + k] * fB[k * 16 + j];
+        double e = std::abs(hD[i * 16 + j] - ref);
+        if (e > mfma_err) mfma_err = e;
+      }
+    if (mfma_err > 1e-3) {
+      std::printf("numerics: bf16 MFMA FAIL (err %g)\n", mfma_err);
+      return false;
+    }
+  }
+  // --- MX-fp8 identity tile: D must equal B rows exactly
+  double mx_err = 0;
+  {
+    DevBuf<uint8_t> A, B;
+    DevBuf<float> D;
+    (void)A.alloc(16 * 128);
+    (void)B.alloc(16 * 128);
+    (void)D.alloc(16 * 16 * 4);
+    std::vector<uint8_t> hA(16 * 128, 0), hB(16 * 128);
+    for (int i = 0; i < 16; ++i) hA[i * 128 + i] = 0x38;  // e4m3 1.0 on diag
+    // B values: exact small e4m3 codes, col-major pack, asymmetric
+    std::vector<float> fB(128 * 16);
+    const float lut[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
+    for (int k = 0; k < 128; ++k)
+      for (int j = 0; j < 16; ++j) {
+        int code = (k * 7 + j * 3) % 16;  // uses sign bit too
+        float v = lut[code & 7] * ((code & 8) ? -1.f : 1.f);
+        fB[k * 16 + j] = v;
+        // e4m3 encodings of the lut: 0,0x30,0x38,0x3c,0x40,0x44,0x48,0x4c
+        const uint8_t enc[8] = {0, 0x30, 0x38, 0x3c, 0x40, 0x44, 0x48, 0x4c};
+        hB[j * 128 + k] = enc[code & 7] | ((code & 8) ? 0x80 : 0);
+      }
+    (void)hipMemcpy(A, hA.data(), hA.size(), hipMemcpyHostToDevice);
+    (void)hipMemcpy(B, hB.data(), hB.size(), hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(mx_gemm16_kernel<0>, dim3(1), dim3(64), 0, 0,
+                       (const uint8_t*)A, (const uint8_t*)B, (float*)D);
+    std::vector<float> hD(256);
+    (void)hipMemcpy(hD.data(), D, 256 * 4, hipMemcpyDeviceToHost);
+    for (int i = 0; i < 16; ++i)
+      for (int j = 0; j < 16; ++j) {
+        double e = std::abs(hD[i * 16 + j] - fB[i * 16 + j]);
+        if (e > mx_err) mx_err = e;
+      }
+    if (mx_err != 0.0) {
+      std::printf("numerics: MX-fp8 FAIL (err %g)\n", mx_err);
+      return false;
+    }
+  }
+  std::printf(
+      "numerics: triad exact, bf16 MFMA err %.2g, MX-fp8 identity exact\n",
+      mfma_err);
+  return true;
+}
+
+// ---------------------------------------------------------------------------
+// --memtest: HBM pattern memory test (kernels in memtest_kernels.h).
+// Exit codes: 0 clean, 3 detector self-test failed, 4 data miscompare.
+// ---------------------------------------------------------------------------
+
+// Detector self-test: fill 1 MiB and run the detector drill on it.
 // Returns 0 ok, 3 detector failed, 1 HIP error.
 int mem_selftest(void* d_report) {
   using namespace k3samd_kern;
   const int64_t n_cells = (1 << 20) / 16;
   const MemSpec spec{0x5EEDF00Dull, kMemPatternAddr, 0};
-  void* buf;
-  HIP_CHECK(hipMalloc(&buf, n_cells * 16));
+  DevBuf<void> buf;
+  HIP_CHECK(buf.alloc(n_cells * 16));
   launch_mem_fill(0, buf, n_cells, 0, spec, true);
   HIP_CHECK(hipDeviceSynchronize());
-  const uint64_t g[3] = {0, 4ull * 12345 + 2, 4ull * n_cells - 1};
-  const uint32_t mask[3] = {1u << 0, 1u << 17, 1u << 31};
-  for (int i = 0; i < 3; ++i)
-    if (mem_flip(buf, g[i], mask[i])) return 1;
+  DrillFlip flips[3] = {{0, 0, 1u << 0},
+                        {4ull * 12345 + 2, 0, 1u << 17},
+                        {4ull * n_cells - 1, 0, 1u << 31}};
+  for (DrillFlip& f : flips) {
+    f.expect = memtest_cell(spec, f.index / 4).d[f.index % 4];
+    if (mem_flip(buf, f.index, f.mask)) return 1;
+  }
   if (mem_report_reset(d_report)) return 1;
   launch_mem_verify(0, buf, n_cells, 0, spec, d_report);
   HIP_CHECK(hipGetLastError());
   HostMemReport r;
   HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(buf));
-  int caught = 0;
-  for (int i = 0; i < 3; ++i) {
-    const uint32_t expect = memtest_cell(spec, g[i] / 4).d[g[i] % 4];
-    for (int s = 0; s < r.n_log(); ++s) {
-      const long long* rec = r.v + kMemReportHeader + 3 * s;
-      if ((uint64_t)rec[0] == g[i] && (uint32_t)rec[1] == expect &&
-          (uint32_t)rec[2] == (expect ^ mask[i])) {
-        ++caught;
-        break;
-      }
-    }
-  }
-  bool ok = caught == 3 && r.bad_dwords() == 3 && r.bad_bits() == 3 &&
-            r.first() == g[0] && r.v[4] == 3 &&
-            r.xor_or() == (mask[0] | mask[1] | mask[2]);
-  if (!ok) {
+  int caught;
+  if (!drill_passed(r, flips, &caught)) {
     std::printf("memtest selftest: FAIL (caught %d/3, bad_dwords %lld, "
                 "bad_bits %lld, xor_or 0x%08x)\n",
                 caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
@@ -261,32 +367,31 @@ int mem_pattern_dump(char** a) {
   return 0;
 }
 
-int run_memtest(int64_t mib, int vram_percent, int passes, int inject,
-                bool do_check) {
+int run_memtest(const Options& o) {
   using namespace k3samd_kern;
-  void* d_report;
-  HIP_CHECK(hipMalloc(&d_report, sizeof(long long) * kMemReportLen));
-  if (do_check) {
+  const int passes = o.passes, inject = o.inject;
+  DevBuf<long long> d_report;
+  HIP_CHECK(d_report.alloc(sizeof(long long) * kMemReportLen));
+  if (o.do_check) {
     int rc = mem_selftest(d_report);
     if (rc) return rc;
   }
 
-  size_t bytes = (size_t)mib << 20;
-  if (vram_percent > 0) {
+  size_t bytes = (size_t)o.mib << 20;
+  if (o.vram_percent > 0) {
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    bytes = (free_b / 100 * (size_t)vram_percent) & ~((size_t)(1 << 20) - 1);
+    bytes =
+        (free_b / 100 * (size_t)o.vram_percent) & ~((size_t)(1 << 20) - 1);
   }
   const int64_t n_cells = (int64_t)(bytes / 16);
   if (n_cells < kMemLogSlots) {
     std::fprintf(stderr, "mi-stream: memtest buffer too small\n");
     return 2;
   }
-  void* buf;
-  HIP_CHECK(hipMalloc(&buf, bytes));
-  hipEvent_t ev0, ev1;
-  HIP_CHECK(hipEventCreate(&ev0));
-  HIP_CHECK(hipEventCreate(&ev1));
+  DevBuf<void> buf;
+  HIP_CHECK(buf.alloc(bytes));
+  EventTimer timer;
   if (mem_report_reset(d_report)) return 1;
 
   std::printf("memtest: %.1f MiB, %d pass(es)%s\n", bytes / 1048576.0, passes,
@@ -311,19 +416,17 @@ int run_memtest(int64_t mib, int vram_percent, int passes, int inject,
         {"verify CHECKER", &chk, nullptr},
     };
     for (const Step& st : steps) {
-      HIP_CHECK(hipEventRecord(ev0));
-      if (!st.from)
-        launch_mem_fill(0, buf, n_cells, 0, *st.to, true);
-      else if (!st.to)
-        launch_mem_verify(0, buf, n_cells, 0, *st.from, d_report);
-      else
-        launch_mem_verify_fill(0, buf, n_cells, 0, *st.from, *st.to, d_report,
-                               true);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(ev1));
-      HIP_CHECK(hipEventSynchronize(ev1));
-      float ms;
-      HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+      float ms;  // one timed launch, no warm-up
+      if (timer.best_of(0, 1, [&](bool) {
+            if (!st.from)
+              launch_mem_fill(0, buf, n_cells, 0, *st.to, true);
+            else if (!st.to)
+              launch_mem_verify(0, buf, n_cells, 0, *st.from, d_report);
+            else
+              launch_mem_verify_fill(0, buf, n_cells, 0, *st.from, *st.to,
+                                     d_report, true);
+          }, &ms))
+        return 1;
       const double moved = (st.from && st.to ? 2.0 : 1.0) * (double)bytes;
       if (st.from && !st.to) verify_ms += ms;
       std::printf("| %4d | %-30s | %10.1f |\n", p, st.name, gbps(moved, ms));
@@ -348,7 +451,7 @@ int run_memtest(int64_t mib, int vram_percent, int passes, int inject,
     std::printf("%18s %10s %10s %10s\n", "byte offset", "expected", "actual",
                 "xor");
     for (int i = 0; i < r.n_log(); ++i) {
-      const long long* rec = r.v + kMemReportHeader + 3 * i;
+      const long long* rec = r.log(i);
       std::printf("0x%016llx 0x%08x 0x%08x 0x%08x\n",
                   (unsigned long long)rec[0] * 4, (unsigned)rec[1],
                   (unsigned)rec[2], (unsigned)(rec[1] ^ rec[2]));
@@ -362,8 +465,6 @@ int run_memtest(int64_t mib, int vram_percent, int passes, int inject,
       first_byte, r.xor_or(),
       verify_ms > 0 ? gbps((double)bytes * passes, (float)verify_ms) : 0.0,
       clean ? "true" : "false");
-  HIP_CHECK(hipFree(buf));
-  HIP_CHECK(hipFree(d_report));
   return clean ? 0 : 4;
 }
 
@@ -406,43 +507,37 @@ long long gemm_host_dot(uint64_t seed, uint32_t m, uint32_t n, int64_t k) {
   return s;
 }
 
+// The buffers of one M x N x K problem: bf16 A[M,K] and Bt[N,K], fp32 C
+// and gold, and the per-tile XCC_ID/HW_ID record.
 struct GemmBufs {
-  void *a = nullptr, *bt = nullptr, *c = nullptr, *gold = nullptr;
-  int* where = nullptr;
+  DevBuf<void> a, bt;
+  DevBuf<float> c, gold;
+  DevBuf<int> where;
   int64_t tiles = 0;
+
+  int alloc(int64_t m, int64_t n, int64_t k) {
+    tiles = (m / k3samd_kern::kGemmBM) * (n / k3samd_kern::kGemmBN);
+    HIP_CHECK(a.alloc((size_t)m * k * 2));
+    HIP_CHECK(bt.alloc((size_t)n * k * 2));
+    HIP_CHECK(c.alloc((size_t)m * n * 4));
+    HIP_CHECK(gold.alloc((size_t)m * n * 4));
+    HIP_CHECK(where.alloc((size_t)tiles * 8));
+    HIP_CHECK(hipMemset(c, 0xFF, (size_t)m * n * 4));  // NaN: unwritten != gold
+    HIP_CHECK(hipMemset(where, 0xFF, (size_t)tiles * 8));
+    return 0;
+  }
 };
-
-int gemm_alloc(GemmBufs& g, int64_t m, int64_t n, int64_t k) {
-  g.tiles = (m / k3samd_kern::kGemmBM) * (n / k3samd_kern::kGemmBN);
-  HIP_CHECK(hipMalloc(&g.a, (size_t)m * k * 2));
-  HIP_CHECK(hipMalloc(&g.bt, (size_t)n * k * 2));
-  HIP_CHECK(hipMalloc(&g.c, (size_t)m * n * 4));
-  HIP_CHECK(hipMalloc(&g.gold, (size_t)m * n * 4));
-  HIP_CHECK(hipMalloc(&g.where, (size_t)g.tiles * 8));
-  HIP_CHECK(hipMemset(g.c, 0xFF, (size_t)m * n * 4));  // NaN: unwritten != gold
-  HIP_CHECK(hipMemset(g.where, 0xFF, (size_t)g.tiles * 8));
-  return 0;
-}
-
-int gemm_free(GemmBufs& g) {
-  HIP_CHECK(hipFree(g.a));
-  HIP_CHECK(hipFree(g.bt));
-  HIP_CHECK(hipFree(g.c));
-  HIP_CHECK(hipFree(g.gold));
-  HIP_CHECK(hipFree(g.where));
-  return 0;
-}
 
 // Self-test: (1) a 256x256x128 product, both the MFMA result and the
 // integer gold, against the host integer product of gemm_pattern.h;
-// (2) the detector drill of mem_selftest on C: flip three known bits,
-// require exactly those three back. Returns 0 ok, 3 failed, 1 HIP error.
+// (2) the detector drill on C against the gold.
+// Returns 0 ok, 3 failed, 1 HIP error.
 int gemm_selftest(void* d_report) {
   using namespace k3samd_kern;
   const int64_t m = 256, n = 256, k = 128;
   const uint64_t seed = 0x5EEDF00Dull;
   GemmBufs g;
-  if (gemm_alloc(g, m, n, k)) return 1;
+  if (g.alloc(m, n, k)) return 1;
   launch_gemm_fill(0, g.a, 0, seed, m, k);
   launch_gemm_fill(0, g.bt, 1, seed, n, k);
   launch_gemm_ref_int(0, g.a, g.bt, g.gold, m, n, k);
@@ -476,33 +571,20 @@ int gemm_selftest(void* d_report) {
   std::printf("gemmtest selftest: 256x256x128 MFMA product and integer gold "
               "match the host product exactly\n");
 
-  const uint64_t e[3] = {0, 12345, (uint64_t)(m * n - 1)};
-  const uint32_t mask[3] = {1u << 0, 1u << 17, 1u << 31};
-  for (int i = 0; i < 3; ++i)
-    if (mem_flip(g.c, e[i], mask[i])) return 1;
+  DrillFlip flips[3] = {{0, 0, 1u << 0},
+                        {12345, 0, 1u << 17},
+                        {(uint64_t)(m * n - 1), 0, 1u << 31}};
+  for (DrillFlip& f : flips) {
+    std::memcpy(&f.expect, &hg[f.index], 4);
+    if (mem_flip(g.c, f.index, f.mask)) return 1;
+  }
   if (mem_report_reset(d_report)) return 1;
   launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
   HIP_CHECK(hipGetLastError());
   HostMemReport r;
   HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-  int caught = 0;
-  for (int i = 0; i < 3; ++i) {
-    uint32_t expect;
-    std::memcpy(&expect, &hg[e[i]], 4);
-    for (int s = 0; s < r.n_log(); ++s) {
-      const long long* rec = r.v + kMemReportHeader + 3 * s;
-      if ((uint64_t)rec[0] == e[i] && (uint32_t)rec[1] == expect &&
-          (uint32_t)rec[2] == (expect ^ mask[i])) {
-        ++caught;
-        break;
-      }
-    }
-  }
-  if (gemm_free(g)) return 1;
-  bool ok = caught == 3 && r.bad_dwords() == 3 && r.bad_bits() == 3 &&
-            r.first() == e[0] && r.v[4] == 3 &&
-            r.xor_or() == (mask[0] | mask[1] | mask[2]);
-  if (!ok) {
+  int caught;
+  if (!drill_passed(r, flips, &caught)) {
     std::printf("gemmtest selftest: FAIL (caught %d/3, bad_elems %lld, "
                 "bad_bits %lld, xor_or 0x%08x)\n",
                 caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
@@ -512,36 +594,27 @@ int gemm_selftest(void* d_report) {
   return 0;
 }
 
-// Element index of injected flip i of `inject` (documented: evenly spaced
-// from element 0, bit i % 32).
-uint64_t gemm_inject_elem(int i, int inject, int64_t m, int64_t n) {
-  return (uint64_t)i * ((uint64_t)(m * n) / (uint64_t)inject);
-}
-
-int run_gemmtest(int64_t m, int64_t n, int64_t k, int iters, int seconds,
-                 int inject, bool do_check) {
+int run_gemmtest(const Options& o) {
   using namespace k3samd_kern;
+  const int64_t m = o.gemm_m, n = o.gemm_n, k = o.gemm_k;
+  const int iters = o.gemm_iters, seconds = o.gemm_seconds,
+            inject = o.gemm_inject;
   const uint64_t seed = 0;
-  void* d_report;
-  HIP_CHECK(hipMalloc(&d_report, sizeof(long long) * kMemReportLen));
-  if (do_check) {
+  DevBuf<long long> d_report;
+  HIP_CHECK(d_report.alloc(sizeof(long long) * kMemReportLen));
+  if (o.do_check) {
     int rc = gemm_selftest(d_report);
     if (rc) return rc;
   }
   GemmBufs g;
-  if (gemm_alloc(g, m, n, k)) return 1;
-  hipEvent_t ev0, ev1;
-  HIP_CHECK(hipEventCreate(&ev0));
-  HIP_CHECK(hipEventCreate(&ev1));
+  if (g.alloc(m, n, k)) return 1;
   launch_gemm_fill(0, g.a, 0, seed, m, k);
   launch_gemm_fill(0, g.bt, 1, seed, n, k);
-  HIP_CHECK(hipEventRecord(ev0));
-  launch_gemm_ref_int(0, g.a, g.bt, g.gold, m, n, k);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(ev1));
-  HIP_CHECK(hipEventSynchronize(ev1));
-  float gold_ms;
-  HIP_CHECK(hipEventElapsedTime(&gold_ms, ev0, ev1));
+  float gold_ms;  // one timed launch, no warm-up
+  if (EventTimer().best_of(0, 1, [&](bool) {
+        launch_gemm_ref_int(0, g.a, g.bt, g.gold, m, n, k);
+      }, &gold_ms))
+    return 1;
 
   // gold spot-check: 64 fixed elements against host integer dot products
   // of the generator — independent of the device entirely
@@ -551,8 +624,8 @@ int run_gemmtest(int64_t m, int64_t n, int64_t k, int iters, int seconds,
     const uint32_t col = i == 63 ? (uint32_t)(n - 1)
                                  : (uint32_t)(((uint64_t)i * 0x85EBCA6Bull + 7) % (uint64_t)n);
     float got;
-    HIP_CHECK(hipMemcpy(&got, static_cast<float*>(g.gold) + (size_t)row * n + col,
-                        4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&got, g.gold + (size_t)row * n + col, 4,
+                        hipMemcpyDeviceToHost));
     const long long want = gemm_host_dot(seed, row, col, k);
     if (got != (float)want) {
       std::printf("gemmtest: gold spot-check FAIL at [%u][%u]: device %.1f, "
@@ -565,51 +638,40 @@ int run_gemmtest(int64_t m, int64_t n, int64_t k, int iters, int seconds,
               (long long)m, (long long)n, (long long)k, gold_ms,
               inject ? " [fault injection ON]" : "");
 
-  int card = -1;  // sysfs sampling, best effort (as --burn)
-  {
-    auto topo = k3samd::enumerate_topology(k3samd::default_sysfs_root());
-    if (!topo.gpus.empty()) card = topo.gpus[0].card_index;
-  }
+  ThermalSampler thermal;
   if (mem_report_reset(d_report)) return 1;
   const double flops_per = 2.0 * (double)m * (double)n * (double)k;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto since = [&](std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double>(now() - t).count();
-  };
   std::printf("%6s %10s %12s %6s %7s\n", "t(s)", "iters", "TFLOP/s", "temp",
               "power");
-  long max_temp = -1, max_pw = -1;
   long long done = 0, done_last = 0;
   int batch = 1;
-  const auto t0 = now();
+  const auto t0 = Clock::now();
   auto t_last = t0;
   double next_report = 2.0;
   auto status = [&] {
-    auto st = k3samd::read_runtime_stats(k3samd::default_sysfs_root(), card);
-    if (st.temp_mc > max_temp) max_temp = st.temp_mc;
-    if (st.power_uw > max_pw) max_pw = st.power_uw;
-    const double dt = since(t_last);
-    std::printf("%6.0f %10lld %12.1f %5ldC %6.0fW\n", since(t0), done,
+    thermal.sample();
+    const double dt = seconds_since(t_last);
+    std::printf("%6.0f %10lld %12.1f %s\n", seconds_since(t0), done,
                 dt > 0 ? (done - done_last) * flops_per / dt / 1e12 : 0.0,
-                st.temp_mc < 0 ? -1 : st.temp_mc / 1000,
-                st.power_uw < 0 ? -1.0 : st.power_uw / 1e6);
+                thermal.cells);
     std::fflush(stdout);
     done_last = done;
-    t_last = now();
+    t_last = Clock::now();
   };
-  while (seconds > 0 ? since(t0) < (double)seconds : done < iters) {
+  while (seconds > 0 ? seconds_since(t0) < (double)seconds : done < iters) {
     int todo = batch;
     if (seconds <= 0 && todo > iters - done) todo = (int)(iters - done);
-    const auto tb = now();
+    const auto tb = Clock::now();
     for (int i = 0; i < todo; ++i) {
       launch_gemm_bf16_nt(0, g.a, g.bt, g.c, g.where, m, n, k);
       if (done == 0 && i == 0 && inject > 0) {
-        // operator alerting drill: N single-bit flips at fixed elements of
-        // the first result, before its compare
+        // operator alerting drill: N single-bit flips (bit f % 32) in the
+        // first result before its compare, at elements evenly spaced from 0
+        // as documented
+        const uint64_t step = (uint64_t)(m * n) / (uint64_t)inject;
         HIP_CHECK(hipDeviceSynchronize());
         for (int f = 0; f < inject; ++f)
-          if (mem_flip(g.c, gemm_inject_elem(f, inject, m, n), 1u << (f % 32)))
-            return 1;
+          if (mem_flip(g.c, (uint64_t)f * step, 1u << (f % 32))) return 1;
       }
       launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
     }
@@ -617,16 +679,16 @@ int run_gemmtest(int64_t m, int64_t n, int64_t k, int iters, int seconds,
     HIP_CHECK(hipDeviceSynchronize());
     done += todo;
     // size the batch to ~0.2 s between host syncs
-    const double per = since(tb) / todo;
+    const double per = seconds_since(tb) / todo;
     batch = per > 0 ? (int)(0.2 / per) : 64;
     if (batch < 1) batch = 1;
     if (batch > 64) batch = 64;
-    if (since(t0) >= next_report) {
+    if (seconds_since(t0) >= next_report) {
       status();
       next_report += 2.0;
     }
   }
-  const double total_s = since(t0);
+  const double total_s = seconds_since(t0);
   if (done != done_last) status();  // the tail since the last line
 
   HostMemReport r;
@@ -645,7 +707,7 @@ int run_gemmtest(int64_t m, int64_t n, int64_t k, int iters, int seconds,
     std::printf("gemmtest: MISCOMPARE - %lld element(s), %lld bit(s)\n",
                 r.bad_dwords(), r.bad_bits());
     for (int i = 0; i < r.n_log(); ++i) {
-      const long long* rec = r.v + kMemReportHeader + 3 * i;
+      const long long* rec = r.log(i);
       unsigned hw_id = 0;
       const int xcc = xcc_of((unsigned long long)rec[0], &hw_id);
       std::printf("C[%llu][%llu] expected 0x%08x actual 0x%08x xor 0x%08x "
@@ -666,76 +728,329 @@ int run_gemmtest(int64_t m, int64_t n, int64_t k, int iters, int seconds,
       r.bad_bits(), clean ? -1LL : (long long)(r.first() / (uint64_t)n),
       clean ? -1LL : (long long)(r.first() % (uint64_t)n),
       clean ? -1 : xcc_of(r.first(), nullptr),
-      done * flops_per / total_s / 1e12, gold_ms,
-      max_temp < 0 ? -1 : max_temp / 1000, max_pw < 0 ? -1.0 : max_pw / 1e6,
-      clean ? "true" : "false");
-  if (gemm_free(g)) return 1;
-  HIP_CHECK(hipFree(d_report));
+      done * flops_per / total_s / 1e12, gold_ms, thermal.max_temp_c,
+      thermal.max_power_w, clean ? "true" : "false");
   return clean ? 0 : 4;
 }
 
-}  // namespace
+// ---- STREAM modes ----
 
-int main(int argc, char** argv) {
-  int64_t mib = 1024;
-  int iters = 20;
-  int device = 0;
-  bool do_mfma = true;
-  bool do_check = true;
-  bool tune = false;
-  bool lds_compare = false;
-  bool all_gpus = false;
-  int burn_s = 0;
-  bool memtest = false;
-  int passes = 1, vram_percent = 0, inject = 0;
-  bool gemmtest = false;
-  int64_t gemm_m = 4096, gemm_n = 4096, gemm_k = 4096;
-  int gemm_iters = 0, gemm_seconds = 0, gemm_inject = 0;
+// --all-gpus: concurrent non-temporal triad on every visible GPU (the
+// in-pod demonstration of the headline metric at amd.com/gpu: N): per-GPU
+// buffers + stream, launches overlapped, one global wall-clock.
+int run_all_gpus(const Options& o, int ndev) {
+  const int64_t n = o.mib * (1 << 20) / 4;
+  const int64_t n4 = n / 4;
+  const double step_bytes = 3.0 * n * 4;
+  // Raw pointers with explicit per-device frees below, not DevBuf: a
+  // DevBuf would free under whichever device is current when it dies.
+  std::vector<f4*> A(ndev), B(ndev), C(ndev);
+  std::vector<hipStream_t> streams(ndev);
+  for (int d = 0; d < ndev; ++d) {
+    HIP_CHECK(hipSetDevice(d));
+    HIP_CHECK(hipMalloc(&A[d], n * 4));
+    HIP_CHECK(hipMalloc(&B[d], n * 4));
+    HIP_CHECK(hipMalloc(&C[d], n * 4));
+    HIP_CHECK(hipMemset(B[d], 0x3c, n * 4));
+    HIP_CHECK(hipMemset(C[d], 0x3d, n * 4));
+    HIP_CHECK(hipStreamCreate(&streams[d]));
+  }
+  auto launch_all = [&] {
+    for (int d = 0; d < ndev; ++d) {
+      (void)hipSetDevice(d);
+      k3samd_kern::launch_stream_triad(streams[d], A[d], B[d], C[d], kScalar,
+                                       n4, true);
+    }
+  };
+  auto sync_all = [&] {
+    for (int d = 0; d < ndev; ++d) (void)hipStreamSynchronize(streams[d]);
+  };
+  for (int w = 0; w < 3; ++w) launch_all();
+  sync_all();
+  const auto t0 = Clock::now();
+  for (int it = 0; it < o.iters; ++it) launch_all();
+  sync_all();
+  const double sec = seconds_since(t0);
+  const double agg = ndev * step_bytes * o.iters / sec / 1e9;
+  std::printf("mi-stream all-gpus: %d GPU(s) x %lld MiB, aggregate triad "
+              "%.1f GB/s (%.1f per GPU)\n",
+              ndev, (long long)o.mib, agg, agg / ndev);
+  std::printf("{\"payload\": \"mi-stream\", \"mode\": \"all-gpus\", "
+              "\"n_gpus\": %d, \"aggregate_triad_gbps\": %.1f}\n",
+              ndev, agg);
+  for (int d = 0; d < ndev; ++d) {
+    (void)hipSetDevice(d);
+    (void)hipFree(A[d]); (void)hipFree(B[d]); (void)hipFree(C[d]);
+    (void)hipStreamDestroy(streams[d]);
+  }
+  return 0;
+}
+
+// The three fp32 buffers of --mib MiB each that the single-GPU STREAM
+// modes work on (a = f(b, c)), and the timer they share.
+struct StreamBufs {
+  DevBuf<f4> a, b, c;
+  int64_t n4 = 0;
+  double bytes = 0;  // of one buffer
+  EventTimer timer;
+
+  int init(int64_t mib) {
+    const int64_t n = mib * (1 << 20) / 4;  // fp32 elements
+    n4 = n / 4;
+    bytes = (double)n * 4;
+    HIP_CHECK(a.alloc((size_t)n * 4));
+    HIP_CHECK(b.alloc((size_t)n * 4));
+    HIP_CHECK(c.alloc((size_t)n * 4));
+    HIP_CHECK(hipMemset(b, 0x3c, (size_t)n * 4));
+    HIP_CHECK(hipMemset(c, 0x3d, (size_t)n * 4));
+    return 0;
+  }
+};
+
+// --lds-compare: direct-nt vs LDS-staged triad (SURVEY §2c blueprint
+// comparison). 1 warm-up, best of --iters.
+int run_lds_compare(const Options& o, StreamBufs& s) {
+  using namespace k3samd_kern;
+  float direct_ms, lds_ms;
+  if (s.timer.best_of(1, o.iters, [&](bool) {
+        launch_stream_triad(0, s.a, s.b, s.c, kScalar, s.n4, true);
+      }, &direct_ms) ||
+      s.timer.best_of(1, o.iters, [&](bool) {
+        launch_stream_triad_lds(0, s.a, s.b, s.c, kScalar, s.n4);
+      }, &lds_ms))
+    return 1;
+  const double direct = gbps(3 * s.bytes, direct_ms);
+  const double lds = gbps(3 * s.bytes, lds_ms);
+  std::printf("triad %lld MiB: direct-nt %.1f GB/s | LDS-staged %.1f GB/s "
+              "(%.1f%%)\n",
+              (long long)o.mib, direct, lds, 100.0 * lds / direct);
+  std::printf("{\"payload\": \"mi-stream-lds\", \"direct_gbps\": %.1f, "
+              "\"lds_staged_gbps\": %.1f}\n", direct, lds);
+  return 0;
+}
+
+// --tune: sweep block-size x unroll x grid-occupancy for the grid-stride
+// non-temporal triad; prints GB/s per config (exploration tool). These are
+// the one set of STREAM launches with an explicit (blocks, tpb) grid.
+// 2 warm-ups, best of --iters.
+int run_tune(const Options& o, StreamBufs& s) {
+  using namespace k3samd_kern;
+  f4 *a = s.a, *b = s.b, *c = s.c;
+  std::printf("tune: grid-stride nt triad, %lld MiB buffers\n",
+              (long long)o.mib);
+  std::printf("%8s %6s %8s %10s\n", "tpb", "unroll", "blocks", "GB/s");
+  for (int tpb : {256, 512, 1024}) {
+    for (int wavesper : {4, 8, 16, 32}) {  // blocks = CUs*waves*64/tpb
+      const int blocks = 256 * wavesper * 64 / tpb;
+      double rate[3];
+      int u = 0;
+      for (auto kern : {stream_triad_gs_kernel<true, 1>,
+                        stream_triad_gs_kernel<true, 2>,
+                        stream_triad_gs_kernel<true, 4>}) {
+        float ms;
+        if (s.timer.best_of(2, o.iters, [&](bool) {
+              hipLaunchKernelGGL(kern, dim3(blocks), dim3(tpb), 0, 0, a, b, c,
+                                 kScalar, s.n4);
+            }, &ms))
+          return 1;
+        rate[u++] = gbps(3 * s.bytes, ms);
+      }
+      std::printf("%8d %6d %8d  U1 %8.1f U2 %8.1f U4 %8.1f\n", tpb, 1, blocks,
+                  rate[0], rate[1], rate[2]);
+    }
+  }
+  return 0;
+}
+
+// --burn: saturate HBM (nt triad) and the matrix pipes (bf16 MFMA)
+// concurrently on two streams for --burn seconds, sampling thermals from
+// sysfs. Node-acceptance analog of gpu-burn.
+int run_burn(const Options& o, StreamBufs& s) {
+  using namespace k3samd_kern;
+  hipStream_t s_mem, s_mfma;
+  HIP_CHECK(hipStreamCreate(&s_mem));
+  HIP_CHECK(hipStreamCreate(&s_mfma));
+  const int mf_blocks = 1024, mf_iters = 512;
+  DevBuf<float> mf_out;
+  HIP_CHECK(mf_out.alloc(mf_blocks * sizeof(float)));
+  const double triad_bytes = 3.0 * s.bytes;
+  const double mf_flops =
+      mfma_throughput_flops(kMfmaBf16_16x16x32, mf_blocks, mf_iters);
+  ThermalSampler thermal;
+  const auto t_end = Clock::now() + std::chrono::seconds(o.burn_s);
+  // RAS snapshot before the stress: ECC errors that APPEAR during the
+  // burn are the node-acceptance failure signal
+  k3samd::GpuHealthCounters ras0 =
+      k3samd::read_gpu_health(k3samd::default_sysfs_root(), thermal.card);
+  uint64_t launches = 0, launches_last = 0;  // of each of the two kernels
+  std::printf("burn: %d s of concurrent HBM streaming + bf16 MFMA\n",
+              o.burn_s);
+  std::printf("%6s %12s %12s %6s %7s %6s\n", "t(s)", "GB/s", "TFLOP/s",
+              "temp", "power", "busy");
+  const auto t0 = Clock::now();
+  auto next_report = t0 + std::chrono::seconds(2);
+  auto t_last = t0;
+  while (Clock::now() < t_end) {
+    for (int i = 0; i < 8; ++i) {
+      launch_stream_triad(s_mem, s.a, s.b, s.c, kScalar, s.n4, true);
+      launch_mfma_throughput(s_mfma, kMfmaBf16_16x16x32, mf_out, mf_blocks,
+                             mf_iters);
+      ++launches;
+    }
+    HIP_CHECK(hipStreamSynchronize(s_mem));
+    HIP_CHECK(hipStreamSynchronize(s_mfma));
+    if (Clock::now() >= next_report) {
+      const auto st = thermal.sample();
+      const double dt = seconds_since(t_last);
+      const uint64_t n = launches - launches_last;
+      std::printf("%6.0f %12.1f %12.1f %s %5ld%%\n", seconds_since(t0),
+                  n * triad_bytes / dt / 1e9, n * mf_flops / dt / 1e12,
+                  thermal.cells, st.busy_percent);
+      std::fflush(stdout);
+      launches_last = launches;
+      t_last = Clock::now();
+      next_report += std::chrono::seconds(2);
+    }
+  }
+  const double total_s = seconds_since(t0);
+  k3samd::GpuHealthCounters ras1 =
+      k3samd::read_gpu_health(k3samd::default_sysfs_root(), thermal.card);
+  long d_ue = (ras0.ras_ue >= 0 && ras1.ras_ue >= 0)
+                  ? ras1.ras_ue - ras0.ras_ue : -1;
+  long d_ce = (ras0.ras_ce >= 0 && ras1.ras_ce >= 0)
+                  ? ras1.ras_ce - ras0.ras_ce : -1;
+  bool ras_clean = d_ue <= 0 && d_ce <= 0;
+  if (ras0.ras_present)
+    std::printf("burn RAS delta: ue %+ld ce %+ld (%s)\n", d_ue, d_ce,
+                ras_clean ? "clean" : "ERRORS DURING BURN");
+  std::printf(
+      "{\"payload\": \"mi-burn\", \"seconds\": %.0f, \"avg_triad_gbps\": "
+      "%.1f, \"avg_mfma_tflops\": %.1f, \"max_temp_c\": %ld, "
+      "\"max_power_w\": %.0f, \"ras_delta_ue\": %ld, "
+      "\"ras_delta_ce\": %ld, \"ras_clean\": %s}\n",
+      total_s, launches * triad_bytes / total_s / 1e9,
+      launches * mf_flops / total_s / 1e12, thermal.max_temp_c,
+      thermal.max_power_w, d_ue, d_ce, ras_clean ? "true" : "false");
+  HIP_CHECK(hipStreamDestroy(s_mem));
+  HIP_CHECK(hipStreamDestroy(s_mfma));
+  return 0;
+}
+
+const char* gpu_name(const hipDeviceProp_t& prop) {
+  return prop.name[0] ? prop.name : "AMD GPU";  // some boxes report no name
+}
+
+// Default mode: the STREAM table (2 warm-ups, best of --iters per cell),
+// the MFMA rows (1 warm-up at 256 iterations, best of 3: rides out the
+// clock ramp) and the JSON line.
+int run_stream_table(const Options& o, StreamBufs& s,
+                     const hipDeviceProp_t& prop) {
+  using namespace k3samd_kern;
+  struct Row {
+    const char* name;
+    double bytes;
+    float best_ms[2];  // plain, non-temporal
+  } rows[] = {{"copy", 2 * s.bytes, {}}, {"scale", 2 * s.bytes, {}},
+              {"add", 3 * s.bytes, {}}, {"triad", 3 * s.bytes, {}}};
+  auto launch = [&](int op, bool nt) {
+    switch (op) {
+      case 0: return launch_stream_copy(0, s.a, s.b, s.n4, nt);
+      case 1: return launch_stream_scale(0, s.a, s.c, kScalar, s.n4, nt);
+      case 2: return launch_stream_add(0, s.a, s.b, s.c, s.n4, nt);
+      default: return launch_stream_triad(0, s.a, s.b, s.c, kScalar, s.n4, nt);
+    }
+  };
+  for (int op = 0; op < 4; ++op)
+    for (int nt = 0; nt < 2; ++nt)
+      if (s.timer.best_of(2, o.iters, [&](bool) { launch(op, nt); },
+                          &rows[op].best_ms[nt]))
+        return 1;
+
+  std::printf("+--------+-------------------+-------------------+\n");
+  std::printf("| STREAM | plain GB/s        | non-temporal GB/s |\n");
+  std::printf("+--------+-------------------+-------------------+\n");
+  for (const Row& r : rows)
+    std::printf("| %-6s | %17.1f | %17.1f |\n", r.name,
+                gbps(r.bytes, r.best_ms[0]), gbps(r.bytes, r.best_ms[1]));
+  std::printf("+--------+-------------------+-------------------+\n");
+
+  double mfma_tf = 0;
+  if (o.do_mfma) {
+    // 4096 blocks + 4 chains measured best (tools/mfma_tune.hip sweep:
+    // 2477 TF = 99 % of the 2.5 PF dense peak)
+    const int blocks = 4096, mf_iters = 4096;
+    DevBuf<float> out;
+    HIP_CHECK(out.alloc(blocks * sizeof(float)));
+    const MfmaKind kinds[5] = {kMfmaBf16_16x16x32, kMfmaBf16_32x32x16,
+                               kMfmaMxFp8, kMfmaMxFp6, kMfmaMxFp4};
+    double tf[5];
+    for (int i = 0; i < 5; ++i) {
+      float ms;
+      if (s.timer.best_of(1, 3, [&](bool warm) {
+            launch_mfma_throughput(0, kinds[i], out, blocks,
+                                   warm ? 256 : mf_iters);
+          }, &ms))
+        return 1;
+      tf[i] = tflops(mfma_throughput_flops(kinds[i], blocks, mf_iters), ms);
+    }
+    std::printf("| MFMA bf16 16x16x32: %7.1f TF | 32x32x16: %7.1f TF     |\n",
+                tf[0], tf[1]);
+    std::printf("| MFMA MX 16x16x128  fp8: %6.1f | fp6: %6.1f | fp4: %6.1f |\n",
+                tf[2], tf[3], tf[4]);
+    std::printf("+--------+-------------------+-------------------+\n");
+    mfma_tf = std::max(tf[0], tf[1]);
+  }
+
+  const Row& triad = rows[3];
+  std::printf(
+      "{\"payload\": \"mi-stream\", \"gpu\": \"%s\", \"arch\": \"%s\", "
+      "\"buffer_MiB\": %lld, \"triad_gbps\": %.1f, \"mfma_bf16_tflops\": "
+      "%.1f}\n",
+      gpu_name(prop), prop.gcnArchName, (long long)o.mib,
+      gbps(triad.bytes, std::min(triad.best_ms[0], triad.best_ms[1])),
+      mfma_tf);
+  return 0;
+}
+
+// ---- command line ----
+
+constexpr int kRun = -1;  // parse_options: no exit status yet, go on
+
+// Flags are matched left to right. The two dump flags run (host only) and
+// return as soon as they are reached; an unknown flag, or a flag short of
+// its values, prints the usage line and returns 2 (--help: 0).
+int parse_options(int argc, char** argv, Options& o) {
   for (int i = 1; i < argc; ++i) {
-    if (!std::strcmp(argv[i], "--mib") && i + 1 < argc)
-      mib = std::atoll(argv[++i]);
-    else if (!std::strcmp(argv[i], "--iters") && i + 1 < argc)
-      iters = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--device") && i + 1 < argc)
-      device = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--no-mfma"))
-      do_mfma = false;
-    else if (!std::strcmp(argv[i], "--no-check"))
-      do_check = false;
-    else if (!std::strcmp(argv[i], "--tune"))
-      tune = true;
-    else if (!std::strcmp(argv[i], "--lds-compare"))
-      lds_compare = true;
-    else if (!std::strcmp(argv[i], "--all-gpus"))
-      all_gpus = true;
-    else if (!std::strcmp(argv[i], "--burn") && i + 1 < argc)
-      burn_s = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--memtest"))
-      memtest = true;
-    else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc)
-      passes = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--vram-percent") && i + 1 < argc)
-      vram_percent = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--memtest-inject") && i + 1 < argc)
-      inject = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--memtest-pattern-dump") && i + 5 < argc)
-      return mem_pattern_dump(argv + i + 1);  // host only: before any HIP call
-    else if (!std::strcmp(argv[i], "--gemmtest"))
-      gemmtest = true;
-    else if (!std::strcmp(argv[i], "--gemm-size") && i + 1 < argc)
-      gemm_m = gemm_n = gemm_k = std::atoll(argv[++i]);
-    else if (!std::strcmp(argv[i], "--gemm-mnk") && i + 3 < argc) {
-      gemm_m = std::atoll(argv[++i]);
-      gemm_n = std::atoll(argv[++i]);
-      gemm_k = std::atoll(argv[++i]);
-    } else if (!std::strcmp(argv[i], "--gemm-iters") && i + 1 < argc)
-      gemm_iters = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--gemm-seconds") && i + 1 < argc)
-      gemm_seconds = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--gemm-inject") && i + 1 < argc)
-      gemm_inject = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--gemm-operand-dump") && i + 6 < argc)
-      return gemm_operand_dump(argv + i + 1);  // host only: before any HIP call
+    auto flag = [&](const char* name, int n_values = 0) {
+      return !std::strcmp(argv[i], name) && i + n_values < argc;
+    };
+    if (flag("--mib", 1)) o.mib = std::atoll(argv[++i]);
+    else if (flag("--iters", 1)) o.iters = std::atoi(argv[++i]);
+    else if (flag("--device", 1)) o.device = std::atoi(argv[++i]);
+    else if (flag("--no-mfma")) o.do_mfma = false;
+    else if (flag("--no-check")) o.do_check = false;
+    else if (flag("--tune")) o.tune = true;
+    else if (flag("--lds-compare")) o.lds_compare = true;
+    else if (flag("--all-gpus")) o.all_gpus = true;
+    else if (flag("--burn", 1)) o.burn_s = std::atoi(argv[++i]);
+    else if (flag("--memtest")) o.memtest = true;
+    else if (flag("--passes", 1)) o.passes = std::atoi(argv[++i]);
+    else if (flag("--vram-percent", 1)) o.vram_percent = std::atoi(argv[++i]);
+    else if (flag("--memtest-inject", 1)) o.inject = std::atoi(argv[++i]);
+    else if (flag("--memtest-pattern-dump", 5))
+      return mem_pattern_dump(argv + i + 1);
+    else if (flag("--gemmtest")) o.gemmtest = true;
+    else if (flag("--gemm-size", 1))
+      o.gemm_m = o.gemm_n = o.gemm_k = std::atoll(argv[++i]);
+    else if (flag("--gemm-mnk", 3)) {
+      o.gemm_m = std::atoll(argv[++i]);
+      o.gemm_n = std::atoll(argv[++i]);
+      o.gemm_k = std::atoll(argv[++i]);
+    } else if (flag("--gemm-iters", 1)) o.gemm_iters = std::atoi(argv[++i]);
+    else if (flag("--gemm-seconds", 1)) o.gemm_seconds = std::atoi(argv[++i]);
+    else if (flag("--gemm-inject", 1)) o.gemm_inject = std::atoi(argv[++i]);
+    else if (flag("--gemm-operand-dump", 6))
+      return gemm_operand_dump(argv + i + 1);
     else {
       std::printf("mi-stream [--mib N] [--iters N] [--device D] [--no-mfma]"
                   " [--tune] [--lds-compare] [--all-gpus] [--burn SECONDS]"
@@ -748,21 +1063,25 @@ int main(int argc, char** argv) {
       return !std::strcmp(argv[i], "--help") ? 0 : 2;
     }
   }
+  return kRun;
+}
 
-  if (memtest &&
-      (passes < 1 || mib < 1 || inject < 0 || inject > 16 ||
-       (vram_percent != 0 && (vram_percent < 1 || vram_percent > 90)))) {
+// Range checks of the chosen mode, before any HIP call. Returns 0 or the
+// exit status 2. Also applies the --gemmtest default of one second.
+int validate_options(Options& o) {
+  if (o.memtest &&
+      (o.passes < 1 || o.mib < 1 || o.inject < 0 || o.inject > 16 ||
+       (o.vram_percent != 0 && (o.vram_percent < 1 || o.vram_percent > 90)))) {
     std::fprintf(stderr, "mi-stream: --memtest needs --passes >= 1, --mib >= 1,"
                          " --vram-percent 1..90, --memtest-inject 1..16\n");
     return 2;
   }
-
-  if (gemmtest) {
-    if (gemm_iters == 0 && gemm_seconds == 0) gemm_seconds = 1;  // default
-    if (!k3samd_kern::gemm_shape_ok(gemm_m, gemm_n, gemm_k) ||
-        gemm_k > k3samd_kern::kGemmExactMaxK || gemm_iters < 0 ||
-        gemm_seconds < 0 || (gemm_iters > 0 && gemm_seconds > 0) ||
-        gemm_inject < 0 || gemm_inject > 16) {
+  if (o.gemmtest) {
+    if (o.gemm_iters == 0 && o.gemm_seconds == 0) o.gemm_seconds = 1;
+    if (!k3samd_kern::gemm_shape_ok(o.gemm_m, o.gemm_n, o.gemm_k) ||
+        o.gemm_k > k3samd_kern::kGemmExactMaxK || o.gemm_iters < 0 ||
+        o.gemm_seconds < 0 || (o.gemm_iters > 0 && o.gemm_seconds > 0) ||
+        o.gemm_inject < 0 || o.gemm_inject > 16) {
       std::fprintf(stderr, "mi-stream: --gemmtest needs M and N multiples of"
                            " 128, K a multiple of 64 and <= 32768, one of"
                            " --gemm-iters >= 1 / --gemm-seconds >= 1,"
@@ -770,6 +1089,28 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  return 0;
+}
+
+int print_banner(int device, int ndev, hipDeviceProp_t* prop) {
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipGetDeviceProperties(prop, device));
+  std::printf("mi-stream: %s (%s), %d visible GPU(s), %d CUs, %.0f GiB VRAM\n",
+              gpu_name(*prop), prop->gcnArchName, ndev,
+              prop->multiProcessorCount,
+              (double)prop->totalGlobalMem / (1 << 30));
+  return 0;
+}
+
+}  // namespace
+
+// Exit status: 0 ok, 1 HIP error, 2 usage, 3 an oracle/self-test failed,
+// 4 memtest or gemmtest data miscompare.
+int main(int argc, char** argv) {
+  Options o;
+  int rc = parse_options(argc, argv, o);
+  if (rc != kRun) return rc;
+  if ((rc = validate_options(o)) != 0) return rc;
 
   int ndev = 0;
   HIP_CHECK(hipGetDeviceCount(&ndev));
@@ -778,383 +1119,25 @@ int main(int argc, char** argv) {
     return 1;
   }
 
-  if (all_gpus) {
-    if (do_check && !self_check()) return 3;  // oracle on device 0 first
-    // concurrent non-temporal triad on every visible GPU (the in-pod
-    // demonstration of the headline metric at amd.com/gpu: N): per-GPU
-    // buffers + stream, launches overlapped, one global wall-clock.
-    const int64_t n_ = mib * (1 << 20) / 4;
-    const int64_t n4_ = n_ / 4;
-    const double step_bytes = 3.0 * n_ * 4;
-    std::vector<f4*> A(ndev), B(ndev), C(ndev);
-    std::vector<hipStream_t> streams(ndev);
-    for (int d = 0; d < ndev; ++d) {
-      HIP_CHECK(hipSetDevice(d));
-      HIP_CHECK(hipMalloc(&A[d], n_ * 4));
-      HIP_CHECK(hipMalloc(&B[d], n_ * 4));
-      HIP_CHECK(hipMalloc(&C[d], n_ * 4));
-      HIP_CHECK(hipMemset(B[d], 0x3c, n_ * 4));
-      HIP_CHECK(hipMemset(C[d], 0x3d, n_ * 4));
-      HIP_CHECK(hipStreamCreate(&streams[d]));
-    }
-    dim3 g((uint32_t)k3samd_kern::stream_grid(n4_));
-    dim3 blk(k3samd_kern::kThreadsPerBlock);
-    auto launch_all = [&] {
-      for (int d = 0; d < ndev; ++d) {
-        (void)hipSetDevice(d);
-        k3samd_kern::launch_chunked(n4_, [&](int64_t off, int64_t cnt) {
-          dim3 gc((uint32_t)k3samd_kern::stream_grid(cnt));
-          hipLaunchKernelGGL(k3samd_kern::stream_triad_kernel<true>, gc, blk,
-                             0, streams[d], A[d] + off, B[d] + off,
-                             C[d] + off, 2.5f, cnt);
-        });
-      }
-    };
-    auto sync_all = [&] {
-      for (int d = 0; d < ndev; ++d) (void)hipStreamSynchronize(streams[d]);
-    };
-    for (int w = 0; w < 3; ++w) launch_all();
-    sync_all();
-    auto t0 = std::chrono::steady_clock::now();
-    for (int it = 0; it < iters; ++it) launch_all();
-    sync_all();
-    double sec = std::chrono::duration<double>(
-                     std::chrono::steady_clock::now() - t0).count();
-    double agg = ndev * step_bytes * iters / sec / 1e9;
-    std::printf("mi-stream all-gpus: %d GPU(s) x %lld MiB, aggregate triad "
-                "%.1f GB/s (%.1f per GPU)\n",
-                ndev, (long long)mib, agg, agg / ndev);
-    std::printf("{\"payload\": \"mi-stream\", \"mode\": \"all-gpus\", "
-                "\"n_gpus\": %d, \"aggregate_triad_gbps\": %.1f}\n",
-                ndev, agg);
-    for (int d = 0; d < ndev; ++d) {
-      (void)hipSetDevice(d);
-      (void)hipFree(A[d]); (void)hipFree(B[d]); (void)hipFree(C[d]);
-      (void)hipStreamDestroy(streams[d]);
-    }
-    return 0;
+  // When several mode flags are given, the first in this order wins:
+  // all-gpus, memtest, gemmtest, lds-compare, tune, burn, then the default
+  // table. The order is the one the modes have always had.
+  if (o.all_gpus) {
+    if (o.do_check && !self_check()) return 3;  // oracle on device 0 first
+    return run_all_gpus(o, ndev);
   }
 
-  HIP_CHECK(hipSetDevice(device));
   hipDeviceProp_t prop;
-  HIP_CHECK(hipGetDeviceProperties(&prop, device));
+  if (print_banner(o.device, ndev, &prop)) return 1;
+  // these two run their own self-tests (unless --no-check)
+  if (o.memtest) return run_memtest(o);
+  if (o.gemmtest) return run_gemmtest(o);
 
-  const char* gpu_name =
-      prop.name[0] ? prop.name : "AMD GPU";  // some boxes report no name
-  std::printf("mi-stream: %s (%s), %d visible GPU(s), %d CUs, %.0f GiB VRAM\n",
-              gpu_name, prop.gcnArchName, ndev, prop.multiProcessorCount,
-              (double)prop.totalGlobalMem / (1 << 30));
-
-  // exit 3: an oracle/self-test failed; exit 4: memtest or gemmtest data
-  // miscompare
-  if (memtest) return run_memtest(mib, vram_percent, passes, inject, do_check);
-  if (gemmtest)
-    return run_gemmtest(gemm_m, gemm_n, gemm_k, gemm_iters, gemm_seconds,
-                        gemm_inject, do_check);
-
-  if (do_check && !self_check()) return 3;  // pod log is the oracle
-
-  const int64_t n = mib * (1 << 20) / 4;  // fp32 elements
-  const int64_t n4 = n / 4;
-  const double buf_bytes = (double)n * 4;
-  f4 *a, *b, *c;
-  HIP_CHECK(hipMalloc(&a, buf_bytes));
-  HIP_CHECK(hipMalloc(&b, buf_bytes));
-  HIP_CHECK(hipMalloc(&c, buf_bytes));
-  HIP_CHECK(hipMemset(b, 0x3c, buf_bytes));
-  HIP_CHECK(hipMemset(c, 0x3d, buf_bytes));
-
-  hipEvent_t ev0, ev1;
-  HIP_CHECK(hipEventCreate(&ev0));
-  HIP_CHECK(hipEventCreate(&ev1));
-  dim3 grid((uint32_t)k3samd_kern::stream_grid(n4));
-  dim3 block(k3samd_kern::kThreadsPerBlock);
-  const float s = 2.5f;
-
-  if (lds_compare) {
-    // direct-nt vs LDS-staged triad (SURVEY §2c blueprint comparison)
-    const double bytes = 3 * buf_bytes;
-    auto time_k = [&](auto launch_fn) -> double {
-      launch_fn();
-      (void)hipDeviceSynchronize();
-      float best = 1e30f;
-      for (int it = 0; it < iters; ++it) {
-        (void)hipEventRecord(ev0);
-        launch_fn();
-        (void)hipEventRecord(ev1);
-        (void)hipEventSynchronize(ev1);
-        float ms;
-        (void)hipEventElapsedTime(&ms, ev0, ev1);
-        if (ms < best) best = ms;
-      }
-      return gbps(bytes, best);
-    };
-    double direct = time_k([&] {
-      hipLaunchKernelGGL(k3samd_kern::stream_triad_kernel<true>, grid, block,
-                         0, 0, a, b, c, s, n4);
-    });
-    double lds = time_k([&] {
-      hipLaunchKernelGGL(k3samd_kern::stream_triad_lds_kernel, grid, block,
-                         0, 0, a, b, c, s, n4);
-    });
-    std::printf("triad %lld MiB: direct-nt %.1f GB/s | LDS-staged %.1f GB/s "
-                "(%.1f%%)\n",
-                (long long)mib, direct, lds, 100.0 * lds / direct);
-    std::printf("{\"payload\": \"mi-stream-lds\", \"direct_gbps\": %.1f, "
-                "\"lds_staged_gbps\": %.1f}\n", direct, lds);
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(c);
-    return 0;
-  }
-
-  if (tune) {
-    // sweep block-size x unroll x grid-occupancy for the grid-stride
-    // non-temporal triad; prints GB/s per config (exploration tool)
-    const double bytes = 3 * buf_bytes;
-    auto time_one = [&](auto kern, int tpb, int blocks) -> double {
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(tpb), 0, 0, a, b, c, s, n4);
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(tpb), 0, 0, a, b, c, s, n4);
-      (void)hipDeviceSynchronize();
-      float best = 1e30f;
-      for (int it = 0; it < iters; ++it) {
-        (void)hipEventRecord(ev0);
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(tpb), 0, 0, a, b, c, s, n4);
-        (void)hipEventRecord(ev1);
-        (void)hipEventSynchronize(ev1);
-        float ms;
-        (void)hipEventElapsedTime(&ms, ev0, ev1);
-        if (ms < best) best = ms;
-      }
-      return gbps(bytes, best);
-    };
-    std::printf("tune: grid-stride nt triad, %lld MiB buffers\n",
-                (long long)mib);
-    std::printf("%8s %6s %8s %10s\n", "tpb", "unroll", "blocks", "GB/s");
-    for (int tpb : {256, 512, 1024}) {
-      for (int wavesper : {4, 8, 16, 32}) {  // blocks = CUs*waves*64/tpb
-        int blocks = 256 * wavesper * 64 / tpb;
-        double g1 = time_one(k3samd_kern::stream_triad_gs_kernel<true, 1>,
-                             tpb, blocks);
-        double g2 = time_one(k3samd_kern::stream_triad_gs_kernel<true, 2>,
-                             tpb, blocks);
-        double g4 = time_one(k3samd_kern::stream_triad_gs_kernel<true, 4>,
-                             tpb, blocks);
-        std::printf("%8d %6d %8d  U1 %8.1f U2 %8.1f U4 %8.1f\n", tpb, 1,
-                    blocks, g1, g2, g4);
-      }
-    }
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(c);
-    return 0;
-  }
-
-  if (burn_s > 0) {
-    // Burn-in: saturate HBM (nt triad) and the matrix pipes (bf16 MFMA)
-    // concurrently on two streams for --burn seconds, sampling thermals
-    // from sysfs. Node-acceptance analog of gpu-burn.
-    hipStream_t s_mem, s_mfma;
-    HIP_CHECK(hipStreamCreate(&s_mem));
-    HIP_CHECK(hipStreamCreate(&s_mfma));
-    float* mf_out;
-    const int mf_blocks = 1024;
-    HIP_CHECK(hipMalloc(&mf_out, mf_blocks * sizeof(float)));
-    // resolve our card index for sysfs sampling (best effort)
-    int card = -1;
-    {
-      auto topo = k3samd::enumerate_topology(k3samd::default_sysfs_root());
-      if (!topo.gpus.empty()) card = topo.gpus[0].card_index;
-    }
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t_end = now() + std::chrono::seconds(burn_s);
-    // RAS snapshot before the stress: ECC errors that APPEAR during the
-    // burn are the node-acceptance failure signal
-    k3samd::GpuHealthCounters ras0 =
-        k3samd::read_gpu_health(k3samd::default_sysfs_root(), card);
-    uint64_t triads = 0, mfmas = 0;
-    long max_temp = -1, max_pw = -1;
-    std::printf("burn: %d s of concurrent HBM streaming + bf16 MFMA\n",
-                burn_s);
-    std::printf("%6s %12s %12s %6s %7s %6s\n", "t(s)", "GB/s", "TFLOP/s",
-                "temp", "power", "busy");
-    auto t0 = now();
-    auto next_report = t0 + std::chrono::seconds(2);
-    uint64_t triads_last = 0, mfmas_last = 0;
-    auto t_last = t0;
-    while (now() < t_end) {
-      for (int i = 0; i < 8; ++i) {
-        hipLaunchKernelGGL(k3samd_kern::stream_triad_kernel<true>, grid,
-                           block, 0, s_mem, a, b, c, s, n4);
-        hipLaunchKernelGGL(k3samd_kern::mfma_throughput_kernel,
-                           dim3(mf_blocks), block, 0, s_mfma, mf_out, 512);
-        ++triads;
-        ++mfmas;
-      }
-      HIP_CHECK(hipStreamSynchronize(s_mem));
-      HIP_CHECK(hipStreamSynchronize(s_mfma));
-      if (now() >= next_report) {
-        auto st = k3samd::read_runtime_stats(k3samd::default_sysfs_root(),
-                                             card);
-        double dt = std::chrono::duration<double>(now() - t_last).count();
-        double gbs = (triads - triads_last) * 3.0 * buf_bytes / dt / 1e9;
-        double tf =
-            (mfmas - mfmas_last) * mf_blocks * 4.0 * 4.0 * 16384.0 * 512.0 /
-            dt / 1e12;
-        if (st.temp_mc > max_temp) max_temp = st.temp_mc;
-        if (st.power_uw > max_pw) max_pw = st.power_uw;
-        std::printf("%6.0f %12.1f %12.1f %5ldC %6.0fW %5ld%%\n",
-                    std::chrono::duration<double>(now() - t0).count(), gbs,
-                    tf, st.temp_mc < 0 ? -1 : st.temp_mc / 1000,
-                    st.power_uw < 0 ? -1.0 : st.power_uw / 1e6,
-                    st.busy_percent);
-        std::fflush(stdout);
-        triads_last = triads;
-        mfmas_last = mfmas;
-        t_last = now();
-        next_report += std::chrono::seconds(2);
-      }
-    }
-    double total_s = std::chrono::duration<double>(now() - t0).count();
-    double avg_gbs = triads * 3.0 * buf_bytes / total_s / 1e9;
-    double avg_tf =
-        mfmas * mf_blocks * 4.0 * 4.0 * 16384.0 * 512.0 / total_s / 1e12;
-    k3samd::GpuHealthCounters ras1 =
-        k3samd::read_gpu_health(k3samd::default_sysfs_root(), card);
-    long d_ue = (ras0.ras_ue >= 0 && ras1.ras_ue >= 0)
-                    ? ras1.ras_ue - ras0.ras_ue : -1;
-    long d_ce = (ras0.ras_ce >= 0 && ras1.ras_ce >= 0)
-                    ? ras1.ras_ce - ras0.ras_ce : -1;
-    bool ras_clean = d_ue <= 0 && d_ce <= 0;
-    if (ras0.ras_present)
-      std::printf("burn RAS delta: ue %+ld ce %+ld (%s)\n", d_ue, d_ce,
-                  ras_clean ? "clean" : "ERRORS DURING BURN");
-    std::printf(
-        "{\"payload\": \"mi-burn\", \"seconds\": %.0f, \"avg_triad_gbps\": "
-        "%.1f, \"avg_mfma_tflops\": %.1f, \"max_temp_c\": %ld, "
-        "\"max_power_w\": %.0f, \"ras_delta_ue\": %ld, "
-        "\"ras_delta_ce\": %ld, \"ras_clean\": %s}\n",
-        total_s, avg_gbs, avg_tf, max_temp < 0 ? -1 : max_temp / 1000,
-        max_pw < 0 ? -1.0 : max_pw / 1e6, d_ue, d_ce,
-        ras_clean ? "true" : "false");
-    HIP_CHECK(hipFree(mf_out));
-    HIP_CHECK(hipStreamDestroy(s_mem));
-    HIP_CHECK(hipStreamDestroy(s_mfma));
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(c);
-    return 0;
-  }
-
-  struct Row {
-    const char* name;
-    double bytes;
-    Timing plain, nt;
-  };
-  Row rows[] = {
-      {"copy", 2 * buf_bytes, {}, {}},
-      {"scale", 2 * buf_bytes, {}, {}},
-      {"add", 3 * buf_bytes, {}, {}},
-      {"triad", 3 * buf_bytes, {}, {}},
-  };
-
-  auto launch = [&](int op, bool nt) {
-    using namespace k3samd_kern;
-    // chunked: a flat launch caps at 2^32-1 work-items (AQL grid_size_x),
-    // so buffers >= 64 GiB need more than one dispatch
-    launch_chunked(n4, [&](int64_t off, int64_t cnt) {
-      dim3 g((uint32_t)stream_grid(cnt));
-      if (nt) {
-        switch (op) {
-          case 0: hipLaunchKernelGGL(stream_copy_kernel<true>, g, block, 0, 0, a + off, b + off, cnt); break;
-          case 1: hipLaunchKernelGGL(stream_scale_kernel<true>, g, block, 0, 0, a + off, c + off, s, cnt); break;
-          case 2: hipLaunchKernelGGL(stream_add_kernel<true>, g, block, 0, 0, a + off, b + off, c + off, cnt); break;
-          case 3: hipLaunchKernelGGL(stream_triad_kernel<true>, g, block, 0, 0, a + off, b + off, c + off, s, cnt); break;
-        }
-      } else {
-        switch (op) {
-          case 0: hipLaunchKernelGGL(stream_copy_kernel<false>, g, block, 0, 0, a + off, b + off, cnt); break;
-          case 1: hipLaunchKernelGGL(stream_scale_kernel<false>, g, block, 0, 0, a + off, c + off, s, cnt); break;
-          case 2: hipLaunchKernelGGL(stream_add_kernel<false>, g, block, 0, 0, a + off, b + off, c + off, cnt); break;
-          case 3: hipLaunchKernelGGL(stream_triad_kernel<false>, g, block, 0, 0, a + off, b + off, c + off, s, cnt); break;
-        }
-      }
-    });
-  };
-
-  for (int op = 0; op < 4; ++op) {
-    for (int nt = 0; nt < 2; ++nt) {
-      launch(op, nt);  // warm
-      launch(op, nt);
-      HIP_CHECK(hipDeviceSynchronize());
-      Timing& t = nt ? rows[op].nt : rows[op].plain;
-      for (int it = 0; it < iters; ++it) {
-        HIP_CHECK(hipEventRecord(ev0));
-        launch(op, nt);
-        HIP_CHECK(hipEventRecord(ev1));
-        HIP_CHECK(hipEventSynchronize(ev1));
-        float ms;
-        HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
-        if (ms < t.best_ms) t.best_ms = ms;
-      }
-    }
-  }
-
-  std::printf("+--------+-------------------+-------------------+\n");
-  std::printf("| STREAM | plain GB/s        | non-temporal GB/s |\n");
-  std::printf("+--------+-------------------+-------------------+\n");
-  for (auto& r : rows) {
-    std::printf("| %-6s | %17.1f | %17.1f |\n", r.name,
-                gbps(r.bytes, r.plain.best_ms), gbps(r.bytes, r.nt.best_ms));
-  }
-  std::printf("+--------+-------------------+-------------------+\n");
-
-  double mfma_tf = 0, mfma32_tf = 0;
-  if (do_mfma) {
-    // 4096 blocks + 4 chains measured best (tools/mfma_tune.hip sweep:
-    // 2477 TF = 99 % of the 2.5 PF dense peak)
-    const int blocks = 4096, mf_iters = 4096;
-    float* out;
-    HIP_CHECK(hipMalloc(&out, blocks * sizeof(float)));
-    auto time_mfma = [&](auto kern, double flops_per_wave_iter,
-                         int accs) -> double {
-      hipLaunchKernelGGL(kern, dim3(blocks), block, 0, 0, out, 256);  // warm
-      (void)hipDeviceSynchronize();
-      float best = 1e30f;
-      for (int rep = 0; rep < 3; ++rep) {  // best-of-3: ride out clock ramp
-        (void)hipEventRecord(ev0);
-        hipLaunchKernelGGL(kern, dim3(blocks), block, 0, 0, out, mf_iters);
-        (void)hipEventRecord(ev1);
-        (void)hipEventSynchronize(ev1);
-        float ms;
-        (void)hipEventElapsedTime(&ms, ev0, ev1);
-        if (ms < best) best = ms;
-      }
-      double flops =
-          (double)blocks * 4 * accs * flops_per_wave_iter * mf_iters;
-      return flops / (best * 1e9);
-    };
-    mfma_tf = time_mfma(k3samd_kern::mfma_throughput_kernel, 16384.0, 4);
-    mfma32_tf = time_mfma(k3samd_kern::mfma_throughput32_kernel, 32768.0, 4);
-    double mx8_tf =
-        time_mfma(k3samd_kern::mfma_throughput_mx_kernel<0>, 65536.0, 4);
-    double mx6_tf =
-        time_mfma(k3samd_kern::mfma_throughput_mx_kernel<2>, 65536.0, 4);
-    double mx4_tf =
-        time_mfma(k3samd_kern::mfma_throughput_mx_kernel<4>, 65536.0, 4);
-    std::printf("| MFMA bf16 16x16x32: %7.1f TF | 32x32x16: %7.1f TF     |\n",
-                mfma_tf, mfma32_tf);
-    std::printf("| MFMA MX 16x16x128  fp8: %6.1f | fp6: %6.1f | fp4: %6.1f |\n",
-                mx8_tf, mx6_tf, mx4_tf);
-    std::printf("+--------+-------------------+-------------------+\n");
-    if (mfma32_tf > mfma_tf) mfma_tf = mfma32_tf;
-    HIP_CHECK(hipFree(out));
-  }
-
-  double triad_best =
-      gbps(rows[3].bytes, std::min(rows[3].plain.best_ms, rows[3].nt.best_ms));
-  std::printf(
-      "{\"payload\": \"mi-stream\", \"gpu\": \"%s\", \"arch\": \"%s\", "
-      "\"buffer_MiB\": %lld, \"triad_gbps\": %.1f, \"mfma_bf16_tflops\": "
-      "%.1f}\n",
-      gpu_name, prop.gcnArchName, (long long)mib, triad_best, mfma_tf);
-
-  HIP_CHECK(hipFree(a));
-  HIP_CHECK(hipFree(b));
-  HIP_CHECK(hipFree(c));
-  return 0;
+  if (o.do_check && !self_check()) return 3;  // pod log is the oracle
+  StreamBufs s;
+  if (s.init(o.mib)) return 1;
+  if (o.lds_compare) return run_lds_compare(o, s);
+  if (o.tune) return run_tune(o, s);
+  if (o.burn_s > 0) return run_burn(o, s);
+  return run_stream_table(o, s, prop);
 }

@@ -61,6 +61,51 @@ def test_mi_stream_burn_short():
     assert j["avg_mfma_tflops"] > 50
 
 
+def _mi_stream_small(*flags):
+    """One mi-stream mode at 64 MiB x 2 iterations: the buffers sit in
+    cache there, so these tests assert structure, never a rate floor."""
+    proc = subprocess.run([str(BIN / "mi-stream"), "--mib", "64",
+                           "--iters", "2", *flags],
+                          capture_output=True, text=True, timeout=120)
+    assert proc.returncode == 0, proc.stderr
+    return proc.stdout.strip().splitlines()
+
+
+@requires_gpu
+def test_mi_stream_lds_compare():
+    lines = _mi_stream_small("--lds-compare")
+    assert any(ln.startswith("numerics: triad exact") for ln in lines)
+    j = json.loads(lines[-1])
+    assert j["payload"] == "mi-stream-lds"
+    assert j["direct_gbps"] > 0 and j["lds_staged_gbps"] > 0, j
+
+
+@requires_gpu
+def test_mi_stream_tune():
+    lines = _mi_stream_small("--tune")
+    assert "tune: grid-stride nt triad, 64 MiB buffers" in lines
+    assert ["tpb", "unroll", "blocks", "GB/s"] in [ln.split() for ln in lines]
+    assert not any(ln.startswith("{") for ln in lines)  # no JSON line
+    rows = [ln.split() for ln in lines if " U1 " in ln]
+    # 3 block sizes x 4 occupancies: tpb, unroll, blocks, U1 r, U2 r, U4 r
+    assert [(int(r[0]), int(r[2])) for r in rows] == \
+        [(tpb, 256 * waves * 64 // tpb)
+         for tpb in (256, 512, 1024) for waves in (4, 8, 16, 32)]
+    for r in rows:
+        assert r[3:9:2] == ["U1", "U2", "U4"], r
+        assert all(float(rate) > 0 for rate in r[4:9:2]), r
+
+
+@requires_gpu
+def test_mi_stream_no_mfma_no_check():
+    lines = _mi_stream_small("--no-mfma", "--no-check")
+    assert not any("numerics:" in ln for ln in lines)
+    assert not any("MFMA" in ln for ln in lines)
+    j = json.loads(lines[-1])
+    assert j["payload"] == "mi-stream"
+    assert j["mfma_bf16_tflops"] == 0.0
+
+
 @requires_gpu
 def test_mi_allreduce_single_gpu():
     proc = subprocess.run([str(BIN / "mi-allreduce"), "--ngpus", "1",
