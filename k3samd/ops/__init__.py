@@ -180,6 +180,44 @@ def buf_compare(buf, expected, report):
     _require_native().buf_compare(buf, expected, report)
 
 
+# ---- verified MX (fp8 / fp4 block-scaled) GEMM (hip/mx_gemm_kernels.h) ----
+
+MX_FMT_FP8 = 0  # e4m3 (OCP e4m3fn), one byte per element
+MX_FMT_FP4 = 4  # e2m1, two elements per byte, low nibble = even k
+MX_EXACT_MAX_K = 8192  # 1024 * K <= 2^23: every partial sum exact in fp32
+
+
+def mx_gemm16_scaled(A, SA, B, SB, fmt):
+    """Single-tile D[16,16] = (A∘SA)[16,128] @ (B∘SB)[128,16] via one
+    v_mfma_scale_f32_16x16x128_f8f6f4 with per-lane scale operands. A and B
+    are packed as for mx_gemm16; SA and SB are uint8 [16,4], the E8M0 scale
+    of (row of A or column of B, block of 32 k)."""
+    return _require_native().mx_gemm16_scaled(A, SA, B, SB, int(fmt))
+
+
+def mx_fill(elems, scales, which, seed, rows, k, fmt):
+    """Write generator elements into the stored [rows, k] uint8 matrix
+    `elems` (k bytes per row for fp8, k/2 for fp4) and its E8M0 scales into
+    `scales` [rows, k/32]: which = 0 is A and SA; which = 1 is Bt and SB,
+    with Bt[n][k] = operand(seed, 1, row=k, col=n)."""
+    _require_native().mx_fill(elems, scales, int(which), int(seed) & _U64,
+                              int(rows), int(k), int(fmt))
+
+
+def mx_gemm_nt(A, SA, Bt, SB, fmt, out=None, where=None):
+    """C[M,N] (fp32) = (A∘SA) @ (Bt∘SB).T with the block-scaled 16x16x128
+    MFMA. M % 128 == N % 128 == 0; K % 128 == 0 (fp8) or K % 256 == 0
+    (fp4). `where` as for gemm_bf16_nt."""
+    return _require_native().mx_gemm_nt(A, SA, Bt, SB, int(fmt), out, where)
+
+
+def mx_gemm_ref_int(A, SA, Bt, SB, fmt, out=None):
+    """The same product by int32 VALU arithmetic (no MFMA), as fp32. For
+    integer-valued fp8 elements or any fp4 codes, scales 127..129,
+    K <= 8192."""
+    return _require_native().mx_gemm_ref_int(A, SA, Bt, SB, int(fmt), out)
+
+
 def mem_report_read(report) -> MemReport:
     """Copy the report to the host (this is the synchronisation point)."""
     r = [int(v) for v in report.cpu().tolist()]

@@ -10,6 +10,7 @@
 
 #include "gemm_kernels.h"
 #include "memtest_kernels.h"
+#include "mx_gemm_kernels.h"
 #include "stream_kernels.h"
 
 namespace {
@@ -101,6 +102,47 @@ torch::Tensor gemm_result(const c10::optional<torch::Tensor>& out,
   K3_CHECK(o.is_cuda() && o.device() == A.device(),
            "out must be on the same GPU as A");
   return o;
+}
+
+bool is_u8_matrix(const torch::Tensor& t) {
+  return t.scalar_type() == torch::kUInt8 && t.dim() == 2;
+}
+
+bool aligned16(const torch::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// Verified-MX-GEMM operands: packed elements A [M, KB] and Bt [N, KB]
+// (KB = K bytes for fp8, K / 2 for fp4) with E8M0 scales SA [M, K/32] and
+// SB [N, K/32], all uint8, contiguous, A and Bt 16-byte aligned, meeting
+// mx_gemm_nt_kernel's shape contract. Device checks come last.
+GemmDims check_mx_operands(const torch::Tensor& A, const torch::Tensor& SA,
+                           const torch::Tensor& Bt, const torch::Tensor& SB,
+                           int64_t fmt) {
+  K3_CHECK(k3samd_kern::mx_fmt_ok((int)fmt),
+           "fmt must be 0 (fp8 e4m3) or 4 (fp4 e2m1)");
+  K3_CHECK(is_u8_matrix(A) && is_u8_matrix(SA) && is_u8_matrix(Bt) &&
+               is_u8_matrix(SB),
+           "A, SA, Bt and SB must be 2-D uint8");
+  K3_CHECK(A.is_contiguous() && SA.is_contiguous() && Bt.is_contiguous() &&
+               SB.is_contiguous(),
+           "A, SA, Bt and SB must be contiguous");
+  K3_CHECK(A.size(1) == Bt.size(1), "A and Bt disagree on K");
+  GemmDims d{A.size(0), Bt.size(0), fmt == 4 ? 2 * A.size(1) : A.size(1)};
+  K3_CHECK(k3samd_kern::mx_shape_ok((int)fmt, d.m, d.n, d.k),
+           "mx gemm shape contract: M % 128 == 0, N % 128 == 0, K % 128 == 0 "
+           "(fp8) or K % 256 == 0 (fp4), all > 0");
+  K3_CHECK(SA.size(0) == d.m && SA.size(1) == d.k / 32 && SB.size(0) == d.n &&
+               SB.size(1) == d.k / 32,
+           "scales must be SA [M, K/32] and SB [N, K/32]");
+  K3_CHECK(aligned16(A) && aligned16(Bt),
+           "A and Bt data pointers must be 16-byte aligned");
+  K3_CHECK(A.is_cuda() && SA.is_cuda() && Bt.is_cuda() && SB.is_cuda(),
+           "A, SA, Bt and SB must be on GPU");
+  K3_CHECK(A.device() == SA.device() && A.device() == Bt.device() &&
+               A.device() == SB.device(),
+           "A, SA, Bt and SB must be on the same GPU");
+  return d;
 }
 
 }  // namespace
@@ -333,6 +375,121 @@ void buf_compare(torch::Tensor buf, torch::Tensor expected,
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+// ---- verified MX (fp8 / fp4 block-scaled) MFMA GEMM (mx_gemm_kernels.h) ----
+// Like the bf16 ops, none of these synchronise with the host.
+
+// One tile D[16,16] = (A o SA) . (B o SB) with per-lane scale operands.
+// A and B packed as for mx_gemm16 ([16,128] fp8 / [16,64] fp4, B
+// column-major with k contiguous); SA and SB uint8 [16,4]: the E8M0 scale
+// of (row or column, block of 32 k).
+torch::Tensor mx_gemm16_scaled(torch::Tensor A, torch::Tensor SA,
+                               torch::Tensor B, torch::Tensor SB,
+                               int64_t fmt) {
+  K3_CHECK(k3samd_kern::mx_fmt_ok((int)fmt),
+           "fmt must be 0 (fp8 e4m3) or 4 (fp4 e2m1)");
+  K3_CHECK(is_u8_matrix(A) && is_u8_matrix(SA) && is_u8_matrix(B) &&
+               is_u8_matrix(SB),
+           "A, SA, B and SB must be 2-D uint8");
+  K3_CHECK(A.is_contiguous() && SA.is_contiguous() && B.is_contiguous() &&
+               SB.is_contiguous(),
+           "A, SA, B and SB must be contiguous");
+  const int64_t kb = fmt == 0 ? 128 : 64;  // packed bytes along k
+  K3_CHECK(A.size(0) == 16 && A.size(1) == kb && B.size(0) == 16 &&
+               B.size(1) == kb,
+           "A must be [16,KB], B [16,KB] (B column-major-packed)");
+  K3_CHECK(SA.size(0) == 16 && SA.size(1) == 4 && SB.size(0) == 16 &&
+               SB.size(1) == 4,
+           "SA and SB must be [16,4]");
+  K3_CHECK(A.is_cuda() && SA.is_cuda() && B.is_cuda() && SB.is_cuda(),
+           "A, SA, B and SB must be on GPU");
+  K3_CHECK(A.device() == SA.device() && A.device() == B.device() &&
+               A.device() == SB.device(),
+           "A, SA, B and SB must be on the same GPU");
+  auto D = torch::empty({16, 16}, A.options().dtype(torch::kFloat32));
+  k3samd_kern::launch_mx_gemm16_scaled(at::hip::getCurrentHIPStream(),
+                                       (int)fmt, A.data_ptr(), SA.data_ptr(),
+                                       B.data_ptr(), SB.data_ptr(),
+                                       D.data_ptr());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return D;
+}
+
+// `elems` is the stored [rows, k] element matrix (k bytes per row for fp8,
+// k / 2 for fp4) and `scales` its uint8 [rows, k/32]: A and SA for
+// which = 0, Bt and SB for which = 1.
+void mx_fill(torch::Tensor elems, torch::Tensor scales, int64_t which,
+             uint64_t seed, int64_t rows, int64_t k, int64_t fmt) {
+  K3_CHECK(k3samd_kern::mx_fmt_ok((int)fmt),
+           "fmt must be 0 (fp8 e4m3) or 4 (fp4 e2m1)");
+  K3_CHECK(which == 0 || which == 1, "which must be 0 (A) or 1 (Bt)");
+  K3_CHECK(elems.scalar_type() == torch::kUInt8 &&
+               scales.scalar_type() == torch::kUInt8,
+           "elems and scales must be uint8");
+  K3_CHECK(rows > 0 && k > 0 && k % 32 == 0 && rows <= (1 << 24) &&
+               k <= (1 << 24),
+           "rows and k must be > 0 and k a multiple of 32");
+  K3_CHECK(elems.numel() == rows * k3samd_kern::mx_row_bytes((int)fmt, k),
+           "elems must hold rows * k elements");
+  K3_CHECK(scales.numel() == rows * (k / 32),
+           "scales must hold rows * k / 32 bytes");
+  K3_CHECK(scales.is_contiguous(), "scales must be contiguous");
+  check_mem_buf(elems);
+  K3_CHECK(scales.is_cuda() && scales.device() == elems.device(),
+           "scales must be on the same GPU as elems");
+  k3samd_kern::launch_mx_fill(at::hip::getCurrentHIPStream(), elems.data_ptr(),
+                              scales.data_ptr(), (int)which, seed, rows, k,
+                              (int)fmt);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// C[M,N] fp32 = (A o SA) . (Bt o SB)^T on the matrix pipes; any finite
+// element codes and scales. `where` as for gemm_bf16_nt.
+torch::Tensor mx_gemm_nt(torch::Tensor A, torch::Tensor SA, torch::Tensor Bt,
+                         torch::Tensor SB, int64_t fmt,
+                         c10::optional<torch::Tensor> out,
+                         c10::optional<torch::Tensor> where) {
+  GemmDims d = check_mx_operands(A, SA, Bt, SB, fmt);
+  void* where_ptr = nullptr;
+  if (where.has_value()) {
+    const torch::Tensor& w = *where;
+    const int64_t tiles = (d.m / k3samd_kern::kGemmBM) *
+                          (d.n / k3samd_kern::kGemmBN);
+    K3_CHECK(w.scalar_type() == torch::kInt32, "where must be int32");
+    K3_CHECK(w.dim() == 2 && w.size(0) == tiles && w.size(1) == 2 &&
+                 w.is_contiguous(),
+             "where must be a contiguous int32[tiles,2]");
+    K3_CHECK(w.is_cuda() && w.device() == A.device(),
+             "where must be on the same GPU as A");
+    where_ptr = w.data_ptr();
+  }
+  torch::Tensor C = gemm_result(out, A, d);
+  k3samd_kern::launch_mx_gemm_nt(at::hip::getCurrentHIPStream(), (int)fmt,
+                                 A.data_ptr(), SA.data_ptr(), Bt.data_ptr(),
+                                 SB.data_ptr(), C.data_ptr(), where_ptr, d.m,
+                                 d.n, d.k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return C;
+}
+
+// The same product in int32 VALU arithmetic (no MFMA), written as fp32.
+// Elements must decode to integers (fp8) or be any e2m1 code (fp4), scales
+// must be 127..129, and K <= 8192 keeps every sum exactly representable.
+torch::Tensor mx_gemm_ref_int(torch::Tensor A, torch::Tensor SA,
+                              torch::Tensor Bt, torch::Tensor SB, int64_t fmt,
+                              c10::optional<torch::Tensor> out) {
+  K3_CHECK(A.dim() != 2 || (fmt == 4 ? 2 : 1) * A.size(1) <=
+                               k3samd_kern::kMxExactMaxK,
+           "mx_gemm_ref_int needs K <= 8192 (exactness bound 1024*K <= 2^23)");
+  GemmDims d = check_mx_operands(A, SA, Bt, SB, fmt);
+  torch::Tensor gold = gemm_result(out, A, d);
+  k3samd_kern::launch_mx_gemm_ref_int(at::hip::getCurrentHIPStream(), (int)fmt,
+                                      A.data_ptr(), SA.data_ptr(),
+                                      Bt.data_ptr(), SB.data_ptr(),
+                                      gold.data_ptr(), d.m, d.n, d.k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return gold;
+}
+
 // Host-side query: the extension only ships gfx950 code objects, so report
 // whether the active device is gfx950.
 bool has_mfma() {
@@ -379,5 +536,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = py::none());
   m.def("buf_compare", &buf_compare, py::arg("buf"), py::arg("expected"),
         py::arg("report"));
+  m.def("mx_gemm16_scaled", &mx_gemm16_scaled, py::arg("A"), py::arg("SA"),
+        py::arg("B"), py::arg("SB"), py::arg("fmt"));
+  m.def("mx_fill", &mx_fill, py::arg("elems"), py::arg("scales"),
+        py::arg("which"), py::arg("seed"), py::arg("rows"), py::arg("k"),
+        py::arg("fmt"));
+  m.def("mx_gemm_nt", &mx_gemm_nt, py::arg("A"), py::arg("SA"), py::arg("Bt"),
+        py::arg("SB"), py::arg("fmt"), py::arg("out") = py::none(),
+        py::arg("where") = py::none());
+  m.def("mx_gemm_ref_int", &mx_gemm_ref_int, py::arg("A"), py::arg("SA"),
+        py::arg("Bt"), py::arg("SB"), py::arg("fmt"),
+        py::arg("out") = py::none());
   m.attr("MEM_REPORT_LEN") = (int64_t)k3samd_kern::kMemReportLen;
 }
