@@ -218,6 +218,65 @@ def mx_gemm_ref_int(A, SA, Bt, SB, fmt, out=None):
     return _require_native().mx_gemm_ref_int(A, SA, Bt, SB, int(fmt), out)
 
 
+# ---- per-CU self-test (kernels in hip/cu_test_kernels.h) ----
+
+CU_LDS_BYTES = 163840  # the whole LDS of one CU: one workgroup per CU
+CU_LDS_CELLS = CU_LDS_BYTES // 16
+CU_WG_THREADS = 256
+CU_WAVES = 4
+CU_FOLD_CELL_BIT = 1 << 40  # report cell index of the signature's LDS fold
+
+
+def _inject_tensor(inject, cols):
+    """None or a sequence of `cols`-tuples -> None or a CPU int64[n, cols]
+    tensor (an empty list is None)."""
+    if inject is None:
+        return None
+    import torch
+
+    rows = [[int(v) for v in row] for row in inject]
+    if not rows:
+        return None
+    if any(len(row) != cols for row in rows):
+        raise ValueError(f"every inject row must have {cols} entries")
+    return torch.tensor(rows, dtype=torch.int64)
+
+
+def cu_lds_march(report, where, seed, passes=1, stop_after=4, inject=None,
+                 dump=None):
+    """March the whole 160 KiB LDS of every CU that runs a workgroup of the
+    launch: `where` (int32 [wgs, 2]) sets the grid and receives each
+    workgroup's XCC_ID and HW_ID; miscompares accumulate into `report`
+    (dword g: workgroup g // 40960, LDS byte 4 * (g % 40960)). The last
+    pass ends after phase `stop_after` (0..4); `dump` (int32 [wgs, 40960])
+    receives the final LDS content. `inject` is a list of (wg, lds_dword,
+    xor_mask, phase 0..3) planted in pass 0 after that phase's write."""
+    _require_native().cu_lds_march(report, where, int(seed) & _U64,
+                                   int(passes), int(stop_after),
+                                   _inject_tensor(inject, 4), dump)
+
+
+def cu_valu_signature(report, where, seed, rounds, expected, sig_out=None,
+                      inject=None):
+    """Run the VALU signature on every wave of the launch and compare with
+    `expected` (int32 [64, 4] on the GPU, from cu_signature_expected()).
+    `where` (int32 [4 * wgs, 2]) sets the grid and receives each wave's
+    XCC_ID and HW_ID; report cell c = (wg * 4 + wave) * 64 + lane, dword k
+    = datapath (cell CU_FOLD_CELL_BIT | c holds the cross-wave LDS fold).
+    `sig_out` (int32 [256 * wgs, 4]) receives the compared cells; `inject`
+    is a list of (wg, wave, lane, k 0..4, xor_mask)."""
+    _require_native().cu_valu_signature(report, where, int(seed) & _U64,
+                                        int(rounds), expected, sig_out,
+                                        _inject_tensor(inject, 5))
+
+
+def cu_signature_expected(seed, rounds):
+    """The signature of one wave from the host code of hip/cu_pattern.h: a
+    CPU int32 [64, 4] tensor of bit patterns. Needs no GPU."""
+    return _require_native().cu_signature_expected(int(seed) & _U64,
+                                                   int(rounds))
+
+
 def mem_report_read(report) -> MemReport:
     """Copy the report to the host (this is the synchronisation point)."""
     r = [int(v) for v in report.cpu().tolist()]

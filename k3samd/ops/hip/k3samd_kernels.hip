@@ -8,6 +8,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "cu_test_kernels.h"
 #include "gemm_kernels.h"
 #include "memtest_kernels.h"
 #include "mx_gemm_kernels.h"
@@ -143,6 +144,74 @@ GemmDims check_mx_operands(const torch::Tensor& A, const torch::Tensor& SA,
                A.device() == SB.device(),
            "A, SA, Bt and SB must be on the same GPU");
   return d;
+}
+
+// ---- per-CU self-test arguments (cu_test_kernels.h) ----
+// Everything that does not need the device is checked before the device
+// checks, and all of it before any launch.
+
+void check_cu_report_shape(const torch::Tensor& report) {
+  K3_CHECK(report.scalar_type() == torch::kInt64, "report must be int64");
+  K3_CHECK(report.dim() == 1 &&
+               report.numel() == k3samd_kern::kMemReportLen &&
+               report.is_contiguous(),
+           "report must be a contiguous int64[56] from mem_report_new()");
+}
+
+// `where` is int32 [rows, 2] with rows = wgs * per_wg; returns wgs.
+int64_t check_cu_where_shape(const torch::Tensor& where, int64_t per_wg) {
+  K3_CHECK(where.scalar_type() == torch::kInt32, "where must be int32");
+  K3_CHECK(where.dim() == 2 && where.size(1) == 2 && where.is_contiguous() &&
+               where.size(0) >= per_wg && where.size(0) % per_wg == 0 &&
+               k3samd_kern::cu_grid_ok(where.size(0) / per_wg),
+           per_wg == 1
+               ? "where must be a contiguous int32[wgs,2], 1 <= wgs <= 2^20"
+               : "where must be a contiguous int32[4*wgs,2], 1 <= wgs <= 2^20");
+  return where.size(0) / per_wg;
+}
+
+// Inject list: CPU int64 [n, cols], n <= 256, column j in [0, limit[j]).
+// Returns the row count (0 when absent).
+int check_cu_inject(const c10::optional<torch::Tensor>& inject, int64_t cols,
+                    const int64_t* limit) {
+  if (!inject.has_value()) return 0;
+  const torch::Tensor& t = *inject;
+  K3_CHECK(t.scalar_type() == torch::kInt64 && !t.is_cuda(),
+           "inject must be a CPU int64 tensor");
+  K3_CHECK(t.dim() == 2 && t.size(1) == cols && t.is_contiguous() &&
+               t.size(0) <= k3samd_kern::kCuMaxInject,
+           cols == 4 ? "inject must be a contiguous int64[n,4], n <= 256"
+                     : "inject must be a contiguous int64[n,5], n <= 256");
+  const int64_t* v = t.data_ptr<int64_t>();
+  for (int64_t i = 0; i < t.size(0); ++i)
+    for (int64_t j = 0; j < cols; ++j)
+      K3_CHECK(v[i * cols + j] >= 0 && v[i * cols + j] < limit[j],
+               cols == 4 ? "inject row out of range: (wg < wgs, lds_dword < "
+                           "40960, xor_mask < 2^32, phase 0..3)"
+                         : "inject row out of range: (wg < wgs, wave < 4, "
+                           "lane < 64, k 0..4, xor_mask < 2^32)");
+  return (int)t.size(0);
+}
+
+// Optional int32 output of exactly [rows, cols], 16-byte aligned.
+void check_cu_out_shape(const c10::optional<torch::Tensor>& out, int64_t rows,
+                        int64_t cols, const char* msg) {
+  if (!out.has_value()) return;
+  const torch::Tensor& t = *out;
+  K3_CHECK(t.scalar_type() == torch::kInt32 && t.dim() == 2 &&
+               t.size(0) == rows && t.size(1) == cols && t.is_contiguous(),
+           msg);
+  K3_CHECK(aligned16(t), "output data pointer must be 16-byte aligned");
+}
+
+void check_cu_devices(const torch::Tensor& report, const torch::Tensor& where,
+                      const c10::optional<torch::Tensor>& out) {
+  K3_CHECK(where.is_cuda(), "where must be on GPU");
+  K3_CHECK(report.is_cuda() && report.device() == where.device(),
+           "report must be on the same GPU as where");
+  K3_CHECK(!out.has_value() ||
+               (out->is_cuda() && out->device() == where.device()),
+           "dump / sig_out must be on the same GPU as where");
 }
 
 }  // namespace
@@ -490,6 +559,77 @@ torch::Tensor mx_gemm_ref_int(torch::Tensor A, torch::Tensor SA,
   return gold;
 }
 
+// ---- per-CU self-test (cu_test_kernels.h) ----
+// Like the memtest ops these do not synchronise with the host, apart from
+// the copy of a non-empty inject list to the device.
+
+void cu_lds_march(torch::Tensor report, torch::Tensor where, uint64_t seed,
+                  int64_t passes, int64_t stop_after,
+                  c10::optional<torch::Tensor> inject,
+                  c10::optional<torch::Tensor> dump) {
+  check_cu_report_shape(report);
+  const int64_t wgs = check_cu_where_shape(where, 1);
+  K3_CHECK(passes >= 1 && passes <= (1 << 20), "passes must be >= 1 and <= 2^20");
+  K3_CHECK(stop_after >= 0 && stop_after <= 4, "stop_after must be 0..4");
+  const int64_t limit[4] = {wgs, k3samd_kern::kCuLdsDwords, 1ll << 32, 4};
+  const int n_inject = check_cu_inject(inject, 4, limit);
+  check_cu_out_shape(dump, wgs, k3samd_kern::kCuLdsDwords,
+                     "dump must be a contiguous int32[wgs,40960]");
+  check_cu_devices(report, where, dump);
+  torch::Tensor inj;
+  if (n_inject > 0) inj = inject->to(where.device());
+  k3samd_kern::launch_cu_lds_march(
+      at::hip::getCurrentHIPStream(), report.data_ptr(), where.data_ptr(), wgs,
+      seed, (int)passes, (int)stop_after,
+      n_inject > 0 ? inj.data_ptr() : nullptr, n_inject,
+      dump.has_value() ? dump->data_ptr() : nullptr);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void cu_valu_signature(torch::Tensor report, torch::Tensor where, uint64_t seed,
+                       int64_t rounds, torch::Tensor expected,
+                       c10::optional<torch::Tensor> sig_out,
+                       c10::optional<torch::Tensor> inject) {
+  check_cu_report_shape(report);
+  const int64_t wgs = check_cu_where_shape(where, k3samd_kern::kCuWaves);
+  K3_CHECK(rounds >= 1 && rounds <= (1 << 30), "rounds must be >= 1 and <= 2^30");
+  K3_CHECK(expected.scalar_type() == torch::kInt32 && expected.dim() == 2 &&
+               expected.size(0) == k3samd_kern::kCuWaveLanes &&
+               expected.size(1) == 4 && expected.is_contiguous(),
+           "expected must be a contiguous int32[64,4] from "
+           "cu_signature_expected()");
+  K3_CHECK(aligned16(expected),
+           "expected data pointer must be 16-byte aligned");
+  const int64_t limit[5] = {wgs, k3samd_kern::kCuWaves,
+                            k3samd_kern::kCuWaveLanes, 5, 1ll << 32};
+  const int n_inject = check_cu_inject(inject, 5, limit);
+  check_cu_out_shape(sig_out, wgs * k3samd_kern::kCuWgThreads, 4,
+                     "sig_out must be a contiguous int32[256*wgs,4]");
+  check_cu_devices(report, where, sig_out);
+  K3_CHECK(expected.is_cuda() && expected.device() == where.device(),
+           "expected must be on the same GPU as where");
+  torch::Tensor inj;
+  if (n_inject > 0) inj = inject->to(where.device());
+  k3samd_kern::launch_cu_valu_signature(
+      at::hip::getCurrentHIPStream(), report.data_ptr(), where.data_ptr(), wgs,
+      seed, (int)rounds, expected.data_ptr(),
+      sig_out.has_value() ? sig_out->data_ptr() : nullptr,
+      n_inject > 0 ? inj.data_ptr() : nullptr, n_inject);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// Host code only (cu_pattern.h): the 64 cells of one wave as a CPU
+// int32[64,4] of bit patterns. Needs no GPU.
+torch::Tensor cu_signature_expected(uint64_t seed, int64_t rounds) {
+  K3_CHECK(rounds >= 1 && rounds <= (1 << 30), "rounds must be >= 1 and <= 2^30");
+  k3samd_kern::CuSigCell cells[k3samd_kern::kCuWaveLanes];
+  k3samd_kern::cu_signature_wave(seed, (uint32_t)rounds, cells);
+  auto out = torch::empty({k3samd_kern::kCuWaveLanes, 4},
+                          torch::dtype(torch::kInt32));
+  std::memcpy(out.data_ptr(), cells, sizeof(cells));
+  return out;
+}
+
 // Host-side query: the extension only ships gfx950 code objects, so report
 // whether the active device is gfx950.
 bool has_mfma() {
@@ -547,5 +687,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx_gemm_ref_int", &mx_gemm_ref_int, py::arg("A"), py::arg("SA"),
         py::arg("Bt"), py::arg("SB"), py::arg("fmt"),
         py::arg("out") = py::none());
+  m.def("cu_lds_march", &cu_lds_march, py::arg("report"), py::arg("where"),
+        py::arg("seed"), py::arg("passes") = 1, py::arg("stop_after") = 4,
+        py::arg("inject") = py::none(), py::arg("dump") = py::none());
+  m.def("cu_valu_signature", &cu_valu_signature, py::arg("report"),
+        py::arg("where"), py::arg("seed"), py::arg("rounds"),
+        py::arg("expected"), py::arg("sig_out") = py::none(),
+        py::arg("inject") = py::none());
+  m.def("cu_signature_expected", &cu_signature_expected, py::arg("seed"),
+        py::arg("rounds"));
   m.attr("MEM_REPORT_LEN") = (int64_t)k3samd_kern::kMemReportLen;
+  m.attr("CU_LDS_BYTES") = (int64_t)k3samd_kern::kCuLdsBytes;
+  m.attr("CU_LDS_CELLS") = (int64_t)k3samd_kern::kCuLdsCells;
+  m.attr("CU_WG_THREADS") = (int64_t)k3samd_kern::kCuWgThreads;
+  m.attr("CU_WAVES") = (int64_t)k3samd_kern::kCuWaves;
 }

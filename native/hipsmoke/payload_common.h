@@ -1,4 +1,4 @@
-// Pieces the GPU payload programs (mi-stream, mi-mxgemm) share: the HIP
+// Pieces the GPU payload programs (mi-stream, mi-mxgemm, mi-cutest) share: the HIP
 // error macro, an owning device buffer, event timing, sysfs thermal
 // sampling, and the host side of the memtest / gemmtest report with its
 // detector drill. Each payload is one translation unit, so everything here
@@ -143,7 +143,7 @@ int mem_flip(void* buf, uint64_t g, uint32_t mask) {
   return 0;
 }
 
-// Detector drill of the memtest, gemmtest and mxgemmtest self-tests: a
+// Detector drill of the memtest, gemmtest, mxgemmtest and cutest self-tests: a
 // detector that has never fired proves nothing, so each flips three known
 // bits and requires exactly those three back, by count, first index,
 // xor-or and log. `index` ascends; `expect` is the dword before the flip.
