@@ -277,9 +277,108 @@ def cu_signature_expected(seed, rounds):
                                                    int(rounds))
 
 
+# ---- host-link (PCIe) test (kernels in hip/hostlink_kernels.h) ----
+# Host buffers are pinned CPU tensors (tensor.pin_memory()); the kernels run
+# on the current device and stream. `wgs` workgroups of 256 lanes walk the
+# region, so bytes in flight on the link are 256 * 16 * 4 * wgs.
+
+LINK_DEFAULT_WGS = 256  # per direction; link_duplex defaults to twice that
+LINK_MAX_WGS = 4096
+LINK_SLOT_BYTES = 64
+LINK_CHASE_MAX_N = 1 << 26
+LINK_CHASE_MAX_HOPS = 1 << 22
+
+
+def link_pull_verify(host_buf, report, pattern, seed, invert=False,
+                     cell_offset=0, wgs=LINK_DEFAULT_WGS):
+    """The device reads pinned host memory and compares it with the pattern,
+    accumulating into `report` (a GPU mem_report_new() tensor). No host
+    sync."""
+    _require_native().link_pull_verify(host_buf, report, int(pattern),
+                                       int(seed) & _U64, bool(invert),
+                                       int(cell_offset) & _U64, int(wgs))
+
+
+def link_push_fill(host_buf, pattern, seed, invert=False, cell_offset=0,
+                   wgs=LINK_DEFAULT_WGS):
+    """The device stores the pattern into pinned host memory. No host sync:
+    synchronise before the host reads the buffer."""
+    _require_native().link_push_fill(host_buf, int(pattern), int(seed) & _U64,
+                                     bool(invert), int(cell_offset) & _U64,
+                                     int(wgs))
+
+
+def _link_spec(spec):
+    """(pattern, seed, invert[, cell_offset]) -> four checked ints."""
+    pattern, seed, invert, *rest = spec
+    if len(rest) > 1:
+        raise ValueError("a link spec is (pattern, seed, invert[, cell_offset])")
+    return (int(pattern), int(seed) & _U64, bool(invert),
+            int(rest[0]) & _U64 if rest else 0)
+
+
+def link_duplex(pull_buf, report, pull_spec, push_buf, push_spec,
+                wgs=2 * LINK_DEFAULT_WGS):
+    """One launch of `wgs` >= 2 workgroups: the even ones pull-verify
+    `pull_buf` into `report`, the odd ones push-fill `push_buf`, so both
+    directions of the link are loaded at once. The specs are (pattern, seed,
+    invert[, cell_offset]); the two regions must not overlap."""
+    _require_native().link_duplex(pull_buf, report, *_link_spec(pull_spec),
+                                  push_buf, *_link_spec(push_spec), int(wgs))
+
+
+def link_chase(host_buf, n, hops, out):
+    """One lane makes `hops` dependent loads through the `n`-slot chase table
+    in pinned `host_buf` (from link_chase_fill). `out` (GPU int64[4])
+    receives the final index, the XOR of the visited indices, the elapsed
+    wall_clock64 ticks and `hops`."""
+    _require_native().link_chase(host_buf, int(n), int(hops), out)
+
+
+def link_wall_clock_khz(device=0):
+    """wall_clock64 ticks per millisecond of GPU `device` (an index)."""
+    return _require_native().link_wall_clock_khz(int(device))
+
+
+def link_host_fill(buf, pattern, seed, invert=False, cell_offset=0,
+                   threads=0):
+    """Write the pattern into a CPU tensor with up to 16 host threads
+    (0 = chosen from the size). Needs no GPU."""
+    _require_native().link_host_fill(buf, int(pattern), int(seed) & _U64,
+                                     bool(invert), int(cell_offset) & _U64,
+                                     int(threads))
+
+
+def link_host_verify(buf, pattern, seed, invert=False, cell_offset=0,
+                     threads=0) -> MemReport:
+    """Compare a CPU tensor with the pattern on the host. The result does
+    not depend on `threads`; the log holds the 16 lowest bad dwords. Needs
+    no GPU."""
+    return _mem_report_decode(_require_native().link_host_verify(
+        buf, int(pattern), int(seed) & _U64, bool(invert),
+        int(cell_offset) & _U64, int(threads)).tolist())
+
+
+def link_chase_fill(buf, n, seed):
+    """Write the `n`-slot chase table (64 bytes per slot, dword 0 = next
+    index) into a CPU tensor of 64 * n bytes. Needs no GPU."""
+    _require_native().link_chase_fill(buf, int(n), int(seed) & _U64)
+
+
+def link_chase_expected(n, seed, hops):
+    """(final, xor) of `hops` hops from slot 0 of a clean table, from the
+    host code of hip/hostlink_pattern.h. Needs no GPU."""
+    return tuple(_require_native().link_chase_expected(
+        int(n), int(seed) & _U64, int(hops)))
+
+
 def mem_report_read(report) -> MemReport:
     """Copy the report to the host (this is the synchronisation point)."""
-    r = [int(v) for v in report.cpu().tolist()]
+    return _mem_report_decode(report.cpu().tolist())
+
+
+def _mem_report_decode(values) -> MemReport:
+    r = [int(v) for v in values]
     n_log = min(max(r[4], 0), MEM_LOG_SLOTS)
     log = [(r[8 + 3 * i] & _U64, r[9 + 3 * i] & 0xFFFFFFFF,
             r[10 + 3 * i] & 0xFFFFFFFF) for i in range(n_log)]

@@ -10,6 +10,7 @@
 
 #include "cu_test_kernels.h"
 #include "gemm_kernels.h"
+#include "hostlink_kernels.h"
 #include "memtest_kernels.h"
 #include "mx_gemm_kernels.h"
 #include "stream_kernels.h"
@@ -212,6 +213,84 @@ void check_cu_devices(const torch::Tensor& report, const torch::Tensor& where,
   K3_CHECK(!out.has_value() ||
                (out->is_cuda() && out->device() == where.device()),
            "dump / sig_out must be on the same GPU as where");
+}
+
+// ---- host-link test arguments (hostlink_kernels.h) ----
+// Everything that does not need the HIP runtime is checked first, the
+// pinned check comes last, and all of it before any launch.
+
+// A host buffer: contiguous CPU tensor of whole `unit`-byte pieces, at least
+// one, 16-byte aligned. Returns the byte size.
+int64_t check_link_host_shape(const torch::Tensor& t, int64_t unit,
+                              const char* size_msg) {
+  K3_CHECK(!t.is_cuda(), "host buffer must be a CPU tensor");
+  K3_CHECK(t.is_contiguous(), "host buffer must be contiguous");
+  K3_CHECK(t.nbytes() > 0 && t.nbytes() % unit == 0, size_msg);
+  K3_CHECK(aligned16(t), "host buffer data pointer must be 16-byte aligned");
+  return (int64_t)t.nbytes();
+}
+
+constexpr const char* kLinkCellMsg =
+    "host buffer byte size must be a non-zero multiple of 16";
+
+void check_link_wgs(int64_t wgs, int64_t least) {
+  K3_CHECK(wgs >= least && k3samd_kern::link_wgs_ok(wgs),
+           least == 1 ? "wgs must be in 1 .. 4096"
+                      : "duplex wgs must be in 2 .. 4096");
+}
+
+void check_link_report(const torch::Tensor& report) {
+  check_cu_report_shape(report);
+  K3_CHECK(report.is_cuda(), "report must be on GPU");
+}
+
+// With XNACK off a device access to pageable host memory faults the card,
+// so a buffer is accepted only when the runtime reports host memory for its
+// first and last byte and a device pointer exists. Returns that pointer.
+void* link_device_pointer(const torch::Tensor& t) {
+  char* host = static_cast<char*>(t.data_ptr());
+  void* dev[2] = {nullptr, nullptr};
+  bool ok = true;
+  for (int end = 0; end < 2 && ok; ++end) {
+    hipPointerAttribute_t attr;
+    std::memset(&attr, 0, sizeof(attr));
+    char* p = host + (end ? (int64_t)t.nbytes() - 1 : 0);
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+      (void)hipGetLastError();  // an unregistered pointer is not an error here
+      ok = false;
+    } else {
+      ok = attr.type == hipMemoryTypeHost && attr.devicePointer != nullptr;
+      dev[end] = attr.devicePointer;
+    }
+  }
+  ok = ok && static_cast<char*>(dev[1]) - static_cast<char*>(dev[0]) ==
+                 (int64_t)t.nbytes() - 1;
+  K3_CHECK(ok,
+           "host buffer must be pinned (page-locked, device-visible) host "
+           "memory: use tensor.pin_memory() or torch.empty(..., "
+           "pin_memory=True)");
+  return dev[0];
+}
+
+void check_chase_n(int64_t n) {
+  K3_CHECK(k3samd_kern::link_chase_n_ok(n),
+           "chase n must be a power of two in 2 .. 2^26");
+}
+
+void check_chase_hops(int64_t hops) {
+  K3_CHECK(hops >= 1 && hops <= k3samd_kern::kLinkChaseMaxHops,
+           "chase hops must be in 1 .. 2^22");
+}
+
+void check_chase_buf(const torch::Tensor& t, int64_t n) {
+  check_link_host_shape(t, 64, "chase buffer byte size must be 64 * n");
+  K3_CHECK((int64_t)t.nbytes() == 64 * n,
+           "chase buffer byte size must be 64 * n");
+}
+
+void check_link_threads(int64_t threads) {
+  K3_CHECK(threads >= 0 && threads <= k3samd_kern::kLinkMaxHostThreads,
+           "threads must be 0 (automatic) .. 16");
 }
 
 }  // namespace
@@ -630,6 +709,130 @@ torch::Tensor cu_signature_expected(uint64_t seed, int64_t rounds) {
   return out;
 }
 
+// ---- host-link (PCIe) test (hostlink_kernels.h, hostlink_pattern.h) ----
+// The kernels run on the current device and stream and do not synchronise
+// with the host; every host buffer is pinned CPU memory.
+
+void link_pull_verify(torch::Tensor host_buf, torch::Tensor report,
+                      int64_t pattern, uint64_t seed, bool invert,
+                      uint64_t cell_offset, int64_t wgs) {
+  auto spec = make_mem_spec(pattern, seed, invert);
+  check_link_wgs(wgs, 1);
+  const int64_t n_cells = check_link_host_shape(host_buf, 16, kLinkCellMsg) / 16;
+  check_link_report(report);
+  void* dev = link_device_pointer(host_buf);
+  k3samd_kern::launch_link_pull_verify(at::hip::getCurrentHIPStream(), dev,
+                                       n_cells, cell_offset, spec,
+                                       report.data_ptr(), (int)wgs);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void link_push_fill(torch::Tensor host_buf, int64_t pattern, uint64_t seed,
+                    bool invert, uint64_t cell_offset, int64_t wgs) {
+  auto spec = make_mem_spec(pattern, seed, invert);
+  check_link_wgs(wgs, 1);
+  const int64_t n_cells = check_link_host_shape(host_buf, 16, kLinkCellMsg) / 16;
+  void* dev = link_device_pointer(host_buf);
+  k3samd_kern::launch_link_push_fill(at::hip::getCurrentHIPStream(), dev,
+                                     n_cells, cell_offset, spec, (int)wgs);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void link_duplex(torch::Tensor pull_buf, torch::Tensor report,
+                 int64_t pull_pattern, uint64_t pull_seed, bool pull_invert,
+                 uint64_t pull_cell_offset, torch::Tensor push_buf,
+                 int64_t push_pattern, uint64_t push_seed, bool push_invert,
+                 uint64_t push_cell_offset, int64_t wgs) {
+  auto pull_spec = make_mem_spec(pull_pattern, pull_seed, pull_invert);
+  auto push_spec = make_mem_spec(push_pattern, push_seed, push_invert);
+  check_link_wgs(wgs, 2);
+  const int64_t pull_bytes = check_link_host_shape(pull_buf, 16, kLinkCellMsg);
+  const int64_t push_bytes = check_link_host_shape(push_buf, 16, kLinkCellMsg);
+  const auto a = reinterpret_cast<uintptr_t>(pull_buf.data_ptr());
+  const auto b = reinterpret_cast<uintptr_t>(push_buf.data_ptr());
+  K3_CHECK(a + (uintptr_t)pull_bytes <= b || b + (uintptr_t)push_bytes <= a,
+           "duplex pull and push regions must not overlap");
+  check_link_report(report);
+  k3samd_kern::LinkRegion pull{link_device_pointer(pull_buf), pull_bytes / 16,
+                               pull_cell_offset, pull_spec};
+  k3samd_kern::LinkRegion push{link_device_pointer(push_buf), push_bytes / 16,
+                               push_cell_offset, push_spec};
+  k3samd_kern::launch_link_duplex(at::hip::getCurrentHIPStream(), pull, push,
+                                  report.data_ptr(), (int)wgs);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// `out` is a GPU int64[4]: final index, XOR of visited indices,
+// wall_clock64 ticks, hops.
+void link_chase(torch::Tensor host_buf, int64_t n, int64_t hops,
+                torch::Tensor out) {
+  check_chase_n(n);
+  check_chase_hops(hops);
+  check_chase_buf(host_buf, n);
+  K3_CHECK(out.scalar_type() == torch::kInt64 && out.dim() == 1 &&
+               out.numel() == k3samd_kern::kLinkChaseOutLen &&
+               out.is_contiguous(),
+           "out must be a contiguous int64[4]");
+  K3_CHECK(out.is_cuda(), "out must be on GPU");
+  void* dev = link_device_pointer(host_buf);
+  k3samd_kern::launch_link_chase(at::hip::getCurrentHIPStream(), dev,
+                                 (uint32_t)n, (uint64_t)hops, out.data_ptr());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// wall_clock64() ticks per millisecond on `device`.
+int64_t link_wall_clock_khz(int64_t device) {
+  int khz = 0;
+  K3_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate,
+                                 (int)device) == hipSuccess && khz > 0,
+           "the device reports no wall clock rate");
+  return khz;
+}
+
+// Host code only from here (hostlink_pattern.h): no HIP call, no GPU.
+
+void link_host_fill(torch::Tensor buf, int64_t pattern, uint64_t seed,
+                    bool invert, uint64_t cell_offset, int64_t threads) {
+  auto spec = make_mem_spec(pattern, seed, invert);
+  check_link_threads(threads);
+  const int64_t n_cells = check_link_host_shape(buf, 16, kLinkCellMsg) / 16;
+  pybind11::gil_scoped_release nogil;
+  k3samd_kern::host_fill(buf.data_ptr(), n_cells, spec, cell_offset,
+                         (int)threads);
+}
+
+// Returns a CPU int64[56] report (the layout mem_report_read() decodes).
+torch::Tensor link_host_verify(torch::Tensor buf, int64_t pattern,
+                               uint64_t seed, bool invert,
+                               uint64_t cell_offset, int64_t threads) {
+  auto spec = make_mem_spec(pattern, seed, invert);
+  check_link_threads(threads);
+  const int64_t n_cells = check_link_host_shape(buf, 16, kLinkCellMsg) / 16;
+  auto report = torch::empty({k3samd_kern::kMemReportLen},
+                             torch::dtype(torch::kInt64));
+  static_assert(sizeof(long long) == sizeof(int64_t), "report element");
+  auto* r = reinterpret_cast<long long*>(report.data_ptr<int64_t>());
+  k3samd_kern::host_report_reset(r);
+  pybind11::gil_scoped_release nogil;
+  k3samd_kern::host_verify(buf.data_ptr(), n_cells, spec, cell_offset, r,
+                           (int)threads);
+  return report;
+}
+
+void link_chase_fill(torch::Tensor buf, int64_t n, uint64_t seed) {
+  check_chase_n(n);
+  check_chase_buf(buf, n);
+  k3samd_kern::link_chase_fill(buf.data_ptr(), (uint32_t)n, seed);
+}
+
+std::tuple<int64_t, int64_t> link_chase_expected(int64_t n, uint64_t seed,
+                                                 int64_t hops) {
+  check_chase_n(n);
+  check_chase_hops(hops);
+  auto r = k3samd_kern::link_chase_expected((uint32_t)n, seed, (uint64_t)hops);
+  return {(int64_t)r.final_index, (int64_t)r.xor_all};
+}
+
 // Host-side query: the extension only ships gfx950 code objects, so report
 // whether the active device is gfx950.
 bool has_mfma() {
@@ -696,7 +899,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("inject") = py::none());
   m.def("cu_signature_expected", &cu_signature_expected, py::arg("seed"),
         py::arg("rounds"));
-  m.attr("MEM_REPORT_LEN") = (int64_t)k3samd_kern::kMemReportLen;
+  m.def("link_pull_verify", &link_pull_verify, py::arg("host_buf"),
+        py::arg("report"), py::arg("pattern"), py::arg("seed"),
+        py::arg("invert") = false, py::arg("cell_offset") = 0,
+        py::arg("wgs") = k3samd_kern::kLinkDefaultWgs);
+  m.def("link_push_fill", &link_push_fill, py::arg("host_buf"),
+        py::arg("pattern"), py::arg("seed"), py::arg("invert") = false,
+        py::arg("cell_offset") = 0,
+        py::arg("wgs") = k3samd_kern::kLinkDefaultWgs);
+  m.def("link_duplex", &link_duplex, py::arg("pull_buf"), py::arg("report"),
+        py::arg("pull_pattern"), py::arg("pull_seed"), py::arg("pull_invert"),
+        py::arg("pull_cell_offset"), py::arg("push_buf"),
+        py::arg("push_pattern"), py::arg("push_seed"), py::arg("push_invert"),
+        py::arg("push_cell_offset"),
+        py::arg("wgs") = 2 * k3samd_kern::kLinkDefaultWgs);
+  m.def("link_chase", &link_chase, py::arg("host_buf"), py::arg("n"),
+        py::arg("hops"), py::arg("out"));
+  m.def("link_wall_clock_khz", &link_wall_clock_khz, py::arg("device"));
+  m.def("link_host_fill", &link_host_fill, py::arg("buf"), py::arg("pattern"),
+        py::arg("seed"), py::arg("invert") = false,
+        py::arg("cell_offset") = 0, py::arg("threads") = 0);
+  m.def("link_host_verify", &link_host_verify, py::arg("buf"),
+        py::arg("pattern"), py::arg("seed"), py::arg("invert") = false,
+        py::arg("cell_offset") = 0, py::arg("threads") = 0);
+  m.def("link_chase_fill", &link_chase_fill, py::arg("buf"), py::arg("n"),
+        py::arg("seed"));
+  m.def("link_chase_expected", &link_chase_expected, py::arg("n"),
+        py::arg("seed"), py::arg("hops"));
+  m.attr("LINK_DEFAULT_WGS") = (int64_t)k3samd_kern::kLinkDefaultWgs;
+  m.attr("LINK_MAX_WGS") = (int64_t)k3samd_kern::kLinkMaxWgs;
+  m.attr("MEM_REPORT_LEN") =(int64_t)k3samd_kern::kMemReportLen;
   m.attr("CU_LDS_BYTES") = (int64_t)k3samd_kern::kCuLdsBytes;
   m.attr("CU_LDS_CELLS") = (int64_t)k3samd_kern::kCuLdsCells;
   m.attr("CU_WG_THREADS") = (int64_t)k3samd_kern::kCuWgThreads;

@@ -1,4 +1,4 @@
-// Pieces the GPU payload programs (mi-stream, mi-mxgemm, mi-cutest) share: the HIP
+// Pieces the GPU payload programs (mi-stream, mi-mxgemm, mi-cutest, mi-hostlink) share: the HIP
 // error macro, an owning device buffer, event timing, sysfs thermal
 // sampling, and the host side of the memtest / gemmtest report with its
 // detector drill. Each payload is one translation unit, so everything here
