@@ -93,6 +93,12 @@ MEM_REPORT_LEN = 8 + 3 * MEM_LOG_SLOTS
 _U64 = (1 << 64) - 1
 
 
+def _spec4(pattern, seed, invert, cell_offset):
+    """The (pattern, seed, invert, cell_offset) arguments as the native
+    layer takes them: seed and offset wrapped to 64 bits."""
+    return int(pattern), int(seed) & _U64, bool(invert), int(cell_offset) & _U64
+
+
 @dataclass
 class MemReport:
     """Host-side view of the device report tensor."""
@@ -123,16 +129,15 @@ def mem_fill(buf, pattern, seed, invert=False, cell_offset=0,
              nontemporal=True):
     """Store the pattern over `buf` (any contiguous GPU tensor whose byte
     size is a multiple of 16)."""
-    _require_native().mem_fill(buf, int(pattern), int(seed) & _U64,
-                               bool(invert), int(cell_offset) & _U64,
+    _require_native().mem_fill(buf, *_spec4(pattern, seed, invert, cell_offset),
                                bool(nontemporal))
 
 
 def mem_verify(buf, report, pattern, seed, invert=False, cell_offset=0):
     """Compare `buf` with the pattern and accumulate into `report`.
     No host sync: read the report once with mem_report_read()."""
-    _require_native().mem_verify(buf, report, int(pattern), int(seed) & _U64,
-                                 bool(invert), int(cell_offset) & _U64)
+    _require_native().mem_verify(buf, report,
+                                 *_spec4(pattern, seed, invert, cell_offset))
 
 
 def mem_verify_fill(buf, report, old, new, cell_offset=0, nontemporal=True):
@@ -294,18 +299,16 @@ def link_pull_verify(host_buf, report, pattern, seed, invert=False,
     """The device reads pinned host memory and compares it with the pattern,
     accumulating into `report` (a GPU mem_report_new() tensor). No host
     sync."""
-    _require_native().link_pull_verify(host_buf, report, int(pattern),
-                                       int(seed) & _U64, bool(invert),
-                                       int(cell_offset) & _U64, int(wgs))
+    _require_native().link_pull_verify(
+        host_buf, report, *_spec4(pattern, seed, invert, cell_offset), int(wgs))
 
 
 def link_push_fill(host_buf, pattern, seed, invert=False, cell_offset=0,
                    wgs=LINK_DEFAULT_WGS):
     """The device stores the pattern into pinned host memory. No host sync:
     synchronise before the host reads the buffer."""
-    _require_native().link_push_fill(host_buf, int(pattern), int(seed) & _U64,
-                                     bool(invert), int(cell_offset) & _U64,
-                                     int(wgs))
+    _require_native().link_push_fill(
+        host_buf, *_spec4(pattern, seed, invert, cell_offset), int(wgs))
 
 
 def _link_spec(spec):
@@ -313,8 +316,7 @@ def _link_spec(spec):
     pattern, seed, invert, *rest = spec
     if len(rest) > 1:
         raise ValueError("a link spec is (pattern, seed, invert[, cell_offset])")
-    return (int(pattern), int(seed) & _U64, bool(invert),
-            int(rest[0]) & _U64 if rest else 0)
+    return _spec4(pattern, seed, invert, rest[0] if rest else 0)
 
 
 def link_duplex(pull_buf, report, pull_spec, push_buf, push_spec,
@@ -344,9 +346,8 @@ def link_host_fill(buf, pattern, seed, invert=False, cell_offset=0,
                    threads=0):
     """Write the pattern into a CPU tensor with up to 16 host threads
     (0 = chosen from the size). Needs no GPU."""
-    _require_native().link_host_fill(buf, int(pattern), int(seed) & _U64,
-                                     bool(invert), int(cell_offset) & _U64,
-                                     int(threads))
+    _require_native().link_host_fill(
+        buf, *_spec4(pattern, seed, invert, cell_offset), int(threads))
 
 
 def link_host_verify(buf, pattern, seed, invert=False, cell_offset=0,
@@ -355,8 +356,8 @@ def link_host_verify(buf, pattern, seed, invert=False, cell_offset=0,
     not depend on `threads`; the log holds the 16 lowest bad dwords. Needs
     no GPU."""
     return _mem_report_decode(_require_native().link_host_verify(
-        buf, int(pattern), int(seed) & _U64, bool(invert),
-        int(cell_offset) & _U64, int(threads)).tolist())
+        buf, *_spec4(pattern, seed, invert, cell_offset),
+        int(threads)).tolist())
 
 
 def link_chase_fill(buf, n, seed):

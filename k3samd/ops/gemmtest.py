@@ -90,15 +90,25 @@ def gemmtest(m, n, k, iters=1, seed=0, device="cuda:0", gold_hook=None):
     bt = torch.empty((n, k), dtype=torch.bfloat16, device=device)
     ops.gemm_fill(a, 0, seed, m, k)
     ops.gemm_fill(bt, 1, seed, n, k)
-    gold = ops.gemm_ref_int(a, bt)
+    return _verify_loop((a, bt), ops.gemm_ref_int, ops.gemm_bf16_nt, m, n, k,
+                        iters, gold_hook)
+
+
+def _verify_loop(operands, ref, gemm, m, n, k, iters, gold_hook):
+    """The tail gemmtest and mxgemmtest share: gold = ref(*operands), the
+    hook, then `iters` times gemm(*operands, out=c, where=where) -> bitwise
+    compare against gold."""
+    import torch
+
+    gold = ref(*operands)
     if gold_hook is not None:
         gold_hook(gold)
     c = torch.empty_like(gold)
     tiles = (m // ops.GEMM_TILE_M) * (n // ops.GEMM_TILE_N)
-    where = torch.full((tiles, 2), -1, dtype=torch.int32, device=device)
-    report = ops.mem_report_new(a.device)
+    where = torch.full((tiles, 2), -1, dtype=torch.int32, device=gold.device)
+    report = ops.mem_report_new(gold.device)
     for _ in range(int(iters)):
-        ops.gemm_bf16_nt(a, bt, out=c, where=where)
+        gemm(*operands, out=c, where=where)
         ops.buf_compare(c, gold, report)
     rep = ops.mem_report_read(report)
     return rep, 2.0 * m * n * k * int(iters), where.cpu().numpy()

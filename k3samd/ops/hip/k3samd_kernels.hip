@@ -33,14 +33,17 @@ f4* f4_ptr(const torch::Tensor& t) {
   return reinterpret_cast<f4*>(t.data_ptr<float>());
 }
 
+bool aligned16(const torch::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
 // Memory-test target: any contiguous GPU tensor, any dtype, whole 16-byte
 // cells. Shape checks come before the device check so they can be
 // exercised without a GPU; all of them come before any launch.
 int64_t check_mem_buf(const torch::Tensor& t) {
   K3_CHECK(t.is_contiguous(), "buffer must be contiguous");
   K3_CHECK(t.nbytes() % 16 == 0, "buffer byte size must be a multiple of 16");
-  K3_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-           "buffer data pointer must be 16-byte aligned");
+  K3_CHECK(aligned16(t), "buffer data pointer must be 16-byte aligned");
   K3_CHECK(t.is_cuda(), "buffer must be on GPU");
   return (int64_t)(t.nbytes() / 16);
 }
@@ -52,12 +55,17 @@ k3samd_kern::MemSpec make_mem_spec(int64_t pattern, uint64_t seed,
   return k3samd_kern::MemSpec{seed, (int)pattern, invert ? 1 : 0};
 }
 
-void check_mem_report(const torch::Tensor& report, const torch::Tensor& buf) {
+// The report every test accumulates into; each op adds its device check.
+void check_report_shape(const torch::Tensor& report) {
   K3_CHECK(report.scalar_type() == torch::kInt64, "report must be int64");
   K3_CHECK(report.dim() == 1 &&
                report.numel() == k3samd_kern::kMemReportLen &&
                report.is_contiguous(),
            "report must be a contiguous int64[56] from mem_report_new()");
+}
+
+void check_mem_report(const torch::Tensor& report, const torch::Tensor& buf) {
+  check_report_shape(report);
   K3_CHECK(report.is_cuda() && report.device() == buf.device(),
            "report must be on the same GPU as the buffer");
 }
@@ -81,8 +89,7 @@ GemmDims check_gemm_operands(const torch::Tensor& A, const torch::Tensor& Bt) {
   K3_CHECK(k3samd_kern::gemm_shape_ok(d.m, d.n, d.k),
            "gemm shape contract: M % 128 == 0, N % 128 == 0, K % 64 == 0, "
            "all > 0");
-  K3_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(Bt.data_ptr()) % 16 == 0,
+  K3_CHECK(aligned16(A) && aligned16(Bt),
            "A and Bt data pointers must be 16-byte aligned");
   K3_CHECK(A.is_cuda() && Bt.is_cuda(), "A and Bt must be on GPU");
   K3_CHECK(A.device() == Bt.device(), "A and Bt must be on the same GPU");
@@ -99,19 +106,31 @@ torch::Tensor gemm_result(const c10::optional<torch::Tensor>& out,
   K3_CHECK(o.dim() == 2 && o.size(0) == d.m && o.size(1) == d.n,
            "out must be [M,N]");
   K3_CHECK(o.is_contiguous(), "out must be contiguous");
-  K3_CHECK(reinterpret_cast<uintptr_t>(o.data_ptr()) % 16 == 0,
-           "out data pointer must be 16-byte aligned");
+  K3_CHECK(aligned16(o), "out data pointer must be 16-byte aligned");
   K3_CHECK(o.is_cuda() && o.device() == A.device(),
            "out must be on the same GPU as A");
   return o;
 }
 
-bool is_u8_matrix(const torch::Tensor& t) {
-  return t.scalar_type() == torch::kUInt8 && t.dim() == 2;
+// The optional per-tile placement record of gemm_bf16_nt and mx_gemm_nt:
+// int32 [tiles,2] on A's GPU. Returns its data pointer, or null when absent.
+void* check_tile_where(const c10::optional<torch::Tensor>& where,
+                       const GemmDims& d, const torch::Tensor& A) {
+  if (!where.has_value()) return nullptr;
+  const torch::Tensor& w = *where;
+  const int64_t tiles = (d.m / k3samd_kern::kGemmBM) *
+                        (d.n / k3samd_kern::kGemmBN);
+  K3_CHECK(w.scalar_type() == torch::kInt32, "where must be int32");
+  K3_CHECK(w.dim() == 2 && w.size(0) == tiles && w.size(1) == 2 &&
+               w.is_contiguous(),
+           "where must be a contiguous int32[tiles,2]");
+  K3_CHECK(w.is_cuda() && w.device() == A.device(),
+           "where must be on the same GPU as A");
+  return w.data_ptr();
 }
 
-bool aligned16(const torch::Tensor& t) {
-  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+bool is_u8_matrix(const torch::Tensor& t) {
+  return t.scalar_type() == torch::kUInt8 && t.dim() == 2;
 }
 
 // Verified-MX-GEMM operands: packed elements A [M, KB] and Bt [N, KB]
@@ -151,12 +170,8 @@ GemmDims check_mx_operands(const torch::Tensor& A, const torch::Tensor& SA,
 // Everything that does not need the device is checked before the device
 // checks, and all of it before any launch.
 
-void check_cu_report_shape(const torch::Tensor& report) {
-  K3_CHECK(report.scalar_type() == torch::kInt64, "report must be int64");
-  K3_CHECK(report.dim() == 1 &&
-               report.numel() == k3samd_kern::kMemReportLen &&
-               report.is_contiguous(),
-           "report must be a contiguous int64[56] from mem_report_new()");
+void check_cu_rounds(int64_t rounds) {
+  K3_CHECK(rounds >= 1 && rounds <= (1 << 30), "rounds must be >= 1 and <= 2^30");
 }
 
 // `where` is int32 [rows, 2] with rows = wgs * per_wg; returns wgs.
@@ -240,7 +255,7 @@ void check_link_wgs(int64_t wgs, int64_t least) {
 }
 
 void check_link_report(const torch::Tensor& report) {
-  check_cu_report_shape(report);
+  check_report_shape(report);
   K3_CHECK(report.is_cuda(), "report must be on GPU");
 }
 
@@ -469,19 +484,7 @@ torch::Tensor gemm_bf16_nt(torch::Tensor A, torch::Tensor Bt,
                            c10::optional<torch::Tensor> out,
                            c10::optional<torch::Tensor> where) {
   GemmDims d = check_gemm_operands(A, Bt);
-  void* where_ptr = nullptr;
-  if (where.has_value()) {
-    const torch::Tensor& w = *where;
-    const int64_t tiles = (d.m / k3samd_kern::kGemmBM) *
-                          (d.n / k3samd_kern::kGemmBN);
-    K3_CHECK(w.scalar_type() == torch::kInt32, "where must be int32");
-    K3_CHECK(w.dim() == 2 && w.size(0) == tiles && w.size(1) == 2 &&
-                 w.is_contiguous(),
-             "where must be a contiguous int32[tiles,2]");
-    K3_CHECK(w.is_cuda() && w.device() == A.device(),
-             "where must be on the same GPU as A");
-    where_ptr = w.data_ptr();
-  }
+  void* where_ptr = check_tile_where(where, d, A);
   torch::Tensor C = gemm_result(out, A, d);
   k3samd_kern::launch_gemm_bf16_nt(at::hip::getCurrentHIPStream(),
                                    A.data_ptr(), Bt.data_ptr(), C.data_ptr(),
@@ -597,19 +600,7 @@ torch::Tensor mx_gemm_nt(torch::Tensor A, torch::Tensor SA, torch::Tensor Bt,
                          c10::optional<torch::Tensor> out,
                          c10::optional<torch::Tensor> where) {
   GemmDims d = check_mx_operands(A, SA, Bt, SB, fmt);
-  void* where_ptr = nullptr;
-  if (where.has_value()) {
-    const torch::Tensor& w = *where;
-    const int64_t tiles = (d.m / k3samd_kern::kGemmBM) *
-                          (d.n / k3samd_kern::kGemmBN);
-    K3_CHECK(w.scalar_type() == torch::kInt32, "where must be int32");
-    K3_CHECK(w.dim() == 2 && w.size(0) == tiles && w.size(1) == 2 &&
-                 w.is_contiguous(),
-             "where must be a contiguous int32[tiles,2]");
-    K3_CHECK(w.is_cuda() && w.device() == A.device(),
-             "where must be on the same GPU as A");
-    where_ptr = w.data_ptr();
-  }
+  void* where_ptr = check_tile_where(where, d, A);
   torch::Tensor C = gemm_result(out, A, d);
   k3samd_kern::launch_mx_gemm_nt(at::hip::getCurrentHIPStream(), (int)fmt,
                                  A.data_ptr(), SA.data_ptr(), Bt.data_ptr(),
@@ -646,7 +637,7 @@ void cu_lds_march(torch::Tensor report, torch::Tensor where, uint64_t seed,
                   int64_t passes, int64_t stop_after,
                   c10::optional<torch::Tensor> inject,
                   c10::optional<torch::Tensor> dump) {
-  check_cu_report_shape(report);
+  check_report_shape(report);
   const int64_t wgs = check_cu_where_shape(where, 1);
   K3_CHECK(passes >= 1 && passes <= (1 << 20), "passes must be >= 1 and <= 2^20");
   K3_CHECK(stop_after >= 0 && stop_after <= 4, "stop_after must be 0..4");
@@ -669,9 +660,9 @@ void cu_valu_signature(torch::Tensor report, torch::Tensor where, uint64_t seed,
                        int64_t rounds, torch::Tensor expected,
                        c10::optional<torch::Tensor> sig_out,
                        c10::optional<torch::Tensor> inject) {
-  check_cu_report_shape(report);
+  check_report_shape(report);
   const int64_t wgs = check_cu_where_shape(where, k3samd_kern::kCuWaves);
-  K3_CHECK(rounds >= 1 && rounds <= (1 << 30), "rounds must be >= 1 and <= 2^30");
+  check_cu_rounds(rounds);
   K3_CHECK(expected.scalar_type() == torch::kInt32 && expected.dim() == 2 &&
                expected.size(0) == k3samd_kern::kCuWaveLanes &&
                expected.size(1) == 4 && expected.is_contiguous(),
@@ -700,7 +691,7 @@ void cu_valu_signature(torch::Tensor report, torch::Tensor where, uint64_t seed,
 // Host code only (cu_pattern.h): the 64 cells of one wave as a CPU
 // int32[64,4] of bit patterns. Needs no GPU.
 torch::Tensor cu_signature_expected(uint64_t seed, int64_t rounds) {
-  K3_CHECK(rounds >= 1 && rounds <= (1 << 30), "rounds must be >= 1 and <= 2^30");
+  check_cu_rounds(rounds);
   k3samd_kern::CuSigCell cells[k3samd_kern::kCuWaveLanes];
   k3samd_kern::cu_signature_wave(seed, (uint32_t)rounds, cells);
   auto out = torch::empty({k3samd_kern::kCuWaveLanes, 4},

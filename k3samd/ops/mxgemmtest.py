@@ -23,6 +23,7 @@ from __future__ import annotations
 import numpy as np
 
 from k3samd import ops
+from k3samd.ops.gemmtest import _verify_loop
 from k3samd.ops.gemmtest import locate  # noqa: F401  (same tile geometry)
 
 _M32 = np.uint64(0xFFFFFFFF)
@@ -157,15 +158,5 @@ def mxgemmtest(m, n, k, fmt, iters=1, seed=0, device="cuda:0",
     sb = torch.empty((n, k // 32), dtype=torch.uint8, device=device)
     ops.mx_fill(a, sa, 0, seed, m, k, fmt)
     ops.mx_fill(bt, sb, 1, seed, n, k, fmt)
-    gold = ops.mx_gemm_ref_int(a, sa, bt, sb, fmt)
-    if gold_hook is not None:
-        gold_hook(gold)
-    c = torch.empty_like(gold)
-    tiles = (m // ops.GEMM_TILE_M) * (n // ops.GEMM_TILE_N)
-    where = torch.full((tiles, 2), -1, dtype=torch.int32, device=device)
-    report = ops.mem_report_new(a.device)
-    for _ in range(int(iters)):
-        ops.mx_gemm_nt(a, sa, bt, sb, fmt, out=c, where=where)
-        ops.buf_compare(c, gold, report)
-    rep = ops.mem_report_read(report)
-    return rep, 2.0 * m * n * k * int(iters), where.cpu().numpy()
+    return _verify_loop((a, sa, bt, sb, fmt), ops.mx_gemm_ref_int,
+                        ops.mx_gemm_nt, m, n, k, iters, gold_hook)

@@ -165,15 +165,10 @@ int selftest(void* d_report) {
     launch_cu_lds_march(0, d_report, g.lds_where, 3, seed, 1, 4, g.inject, 3,
                         nullptr);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-    int caught;
-    if (!drill_passed(r, flips, &caught)) {
-      std::printf("cutest selftest: FAIL (LDS drill caught %d/3, bad_dwords "
-                  "%lld, bad_bits %lld, xor_or 0x%08x)\n",
-                  caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
-      return 3;
-    }
-    std::printf("cutest selftest: LDS detector caught 3/3 planted flips\n");
+    const int rc = drill_verdict(d_report, flips,
+                                 {"cutest", "LDS drill ", "bad_dwords",
+                                  "LDS detector caught 3/3 planted flips"});
+    if (rc) return rc;
   }
 
   // (3) VALU drill: lane 0 / fp32, a middle lane / fp64 high, lane 63 of
@@ -195,17 +190,10 @@ int selftest(void* d_report) {
     launch_cu_valu_signature(0, d_report, g.valu_where, 3, seed, rounds,
                              g.expected, nullptr, g.inject, 3);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-    int caught;
-    if (!drill_passed(r, flips, &caught)) {
-      std::printf("cutest selftest: FAIL (VALU drill caught %d/3, bad_dwords "
-                  "%lld, bad_bits %lld, xor_or 0x%08x)\n",
-                  caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
-      return 3;
-    }
-    std::printf("cutest selftest: VALU detector caught 3/3 planted flips\n");
+    return drill_verdict(d_report, flips,
+                         {"cutest", "VALU drill ", "bad_dwords",
+                          "VALU detector caught 3/3 planted flips"});
   }
-  return 0;
 }
 
 const char* const kDatapath[5] = {"fp32", "fp64.lo", "fp64.hi", "int",
@@ -407,16 +395,12 @@ int run(const Options& o, int cus) {
   return !clean ? 4 : covered() ? 0 : 5;
 }
 
-constexpr int kRun = -1;  // parse_options: no exit status yet, go on
-
 // Flags are matched left to right. --signature-dump runs (host only) and
 // returns as soon as it is reached; an unknown flag, or a flag short of its
 // values, prints the usage text and returns 2 (--help: 0).
 int parse_options(int argc, char** argv, Options& o) {
   for (int i = 1; i < argc; ++i) {
-    auto flag = [&](const char* name, int n_values = 0) {
-      return !std::strcmp(argv[i], name) && i + n_values < argc;
-    };
+    const FlagMatcher flag{argc, argv, i};
     if (flag("--device", 1)) o.device = std::atoi(argv[++i]);
     else if (flag("--iters", 1)) o.iters = std::atoi(argv[++i]);
     else if (flag("--seconds", 1)) o.seconds = std::atoi(argv[++i]);
@@ -426,10 +410,7 @@ int parse_options(int argc, char** argv, Options& o) {
       o.inject = std::atoi(argv[++i]);
       if (o.inject == 0) o.inject = -1;  // an explicit 0 is out of 1..16
     } else if (flag("--signature-dump", 2)) return signature_dump(argv + i + 1);
-    else {
-      std::printf("%s", kUsage);
-      return !std::strcmp(argv[i], "--help") ? 0 : 2;
-    }
+    else return usage_status(kUsage, argv[i]);
   }
   return kRun;
 }
@@ -458,17 +439,10 @@ int main(int argc, char** argv) {
   if ((rc = validate_options(o)) != 0) return rc;
 
   int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (ndev == 0) {
-    std::fprintf(stderr, "mi-cutest: no GPUs visible\n");
-    return 1;
-  }
   hipDeviceProp_t prop;
-  HIP_CHECK(hipSetDevice(o.device));
-  HIP_CHECK(hipGetDeviceProperties(&prop, o.device));
+  if (open_device(o.device, &ndev, &prop)) return 1;
   std::printf("mi-cutest: %s (%s), %d visible GPU(s), %d CUs, per-CU LDS march "
               "+ VALU signature\n",
-              prop.name[0] ? prop.name : "AMD GPU",  // some boxes report no name
-              prop.gcnArchName, ndev, prop.multiProcessorCount);
+              prop.name, prop.gcnArchName, ndev, prop.multiProcessorCount);
   return run(o, prop.multiProcessorCount);
 }

@@ -155,11 +155,6 @@ void report_merge(HostMemReport& into, const HostMemReport& from) {
                 3 * sizeof(long long));
 }
 
-int report_download(HostMemReport& r, const void* d_report) {
-  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-  return 0;
-}
-
 // N single-bit flips spread from the first dword of the region to the last.
 struct Flip {
   uint64_t g;
@@ -195,7 +190,6 @@ int selftest(void* d_report, void* d_chase_out) {
                 memtest_cell(spec, planted[i].g / 4).d[planted[i].g % 4],
                 planted[i].mask};
   HostMemReport r;
-  int caught;
 
   host_fill(buf.host(), n_cells, spec, 0);
   report_clear(r);
@@ -212,15 +206,11 @@ int selftest(void* d_report, void* d_chase_out) {
   if (mem_report_reset(d_report)) return 1;
   launch_link_pull_verify(0, buf.dev(), n_cells, 0, spec, d_report, 3);
   HIP_CHECK(hipGetLastError());
-  if (report_download(r, d_report)) return 1;
-  if (!drill_passed(r, flips, &caught)) {
-    std::printf("hostlink selftest: FAIL (pull drill caught %d/3, bad_dwords "
-                "%lld, bad_bits %lld, xor_or 0x%08x)\n",
-                caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
-    return 3;
-  }
-  std::printf("hostlink selftest: pull detector caught 3/3 flips planted in "
-              "host memory\n");
+  int rc = drill_verdict(d_report, flips,
+                         {"hostlink", "pull drill ", "bad_dwords",
+                          "pull detector caught 3/3 flips planted in host "
+                          "memory"});
+  if (rc) return rc;
 
   std::memset(buf.host(), 0xFF, (size_t)n_cells * 16);
   launch_link_push_fill(0, buf.dev(), n_cells, 0, spec, 3);
@@ -229,14 +219,10 @@ int selftest(void* d_report, void* d_chase_out) {
   plant(buf.host(), planted);
   report_clear(r);
   host_verify(buf.host(), n_cells, spec, 0, r.v);
-  if (!drill_passed(r, flips, &caught)) {
-    std::printf("hostlink selftest: FAIL (push drill caught %d/3, bad_dwords "
-                "%lld, bad_bits %lld, xor_or 0x%08x)\n",
-                caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
-    return 3;
-  }
-  std::printf("hostlink selftest: host detector caught 3/3 flips planted in "
-              "pushed data\n");
+  rc = drill_verdict(r, flips,
+                     {"hostlink", "push drill ", "bad_dwords",
+                      "host detector caught 3/3 flips planted in pushed data"});
+  if (rc) return rc;
 
   const uint32_t n = 1024;
   const uint64_t hops = 3 * n + 5;
@@ -426,7 +412,7 @@ int run_phase(Link& L, const Options& o, int ph, int pass, Totals& t) {
   }
   HIP_CHECK(hipDeviceSynchronize());
   HostMemReport found;
-  if (report_download(found, L.d_report)) return 1;
+  if (mem_report_download(found, L.d_report)) return 1;
   report_merge(found, host_found);
   const double bytes =
       4.0 * (double)L.nbytes * (ph == kDuplex || ph == kSdmaDuplex ? 2 : 1);
@@ -556,16 +542,12 @@ int run(const Options& o, const std::string& bdf, const k3samd::PcieLink& link,
   return !clean ? 4 : link_gate || rate_gate ? 6 : 0;
 }
 
-constexpr int kRun = -1;  // parse_options: no exit status yet, go on
-
 // Flags are matched left to right. --pattern-dump runs (host only) and
 // returns as soon as it is reached; an unknown flag, or a flag short of its
 // values, prints the usage text and returns 2 (--help: 0).
 int parse_options(int argc, char** argv, Options& o) {
   for (int i = 1; i < argc; ++i) {
-    auto flag = [&](const char* name, int n_values = 0) {
-      return !std::strcmp(argv[i], name) && i + n_values < argc;
-    };
+    const FlagMatcher flag{argc, argv, i};
     if (flag("--device", 1)) o.device = std::atoi(argv[++i]);
     else if (flag("--mib", 1)) o.mib = std::atoll(argv[++i]);
     else if (flag("--passes", 1)) o.passes = std::atoi(argv[++i]);
@@ -585,10 +567,7 @@ int parse_options(int argc, char** argv, Options& o) {
       return pattern_dump_fill(argv + i + 2);
     else if (flag("--pattern-dump", 4) && !std::strcmp(argv[i + 1], "chase"))
       return pattern_dump_chase(argv + i + 2);
-    else {
-      std::printf("%s", kUsage);
-      return !std::strcmp(argv[i], "--help") ? 0 : 2;
-    }
+    else return usage_status(kUsage, argv[i]);
   }
   return kRun;
 }
@@ -627,14 +606,8 @@ int main(int argc, char** argv) {
   if (o.link_info) return link_info(o);
 
   int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (ndev == 0) {
-    std::fprintf(stderr, "mi-hostlink: no GPUs visible\n");
-    return 1;
-  }
   hipDeviceProp_t prop;
-  HIP_CHECK(hipSetDevice(o.device));
-  HIP_CHECK(hipGetDeviceProperties(&prop, o.device));
+  if (open_device(o.device, &ndev, &prop)) return 1;
   char bdf[32] = "";
   HIP_CHECK(hipDeviceGetPCIBusId(bdf, sizeof(bdf), o.device));
   for (char* c = bdf; *c; ++c)  // sysfs names are lower case
@@ -644,8 +617,7 @@ int main(int argc, char** argv) {
   const long numa_node =
       k3samd::read_pcie_device_long(root, bdf, "numa_node", -1);
   std::printf("mi-hostlink: %s (%s), device %d of %d, bdf %s, numa node %ld, ",
-              prop.name[0] ? prop.name : "AMD GPU",  // some boxes report no name
-              prop.gcnArchName, o.device, ndev, bdf, numa_node);
+              prop.name, prop.gcnArchName, o.device, ndev, bdf, numa_node);
   if (link.known)
     std::printf("link Gen%d x%d (%.1f GB/s raw)%s\n", link.gen, link.cur_width,
                 link.raw_gbps,

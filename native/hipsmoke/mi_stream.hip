@@ -32,6 +32,7 @@
 
 #define K3_PAYLOAD_NAME "mi-stream"
 #include "payload_common.h"
+#include "gemm_verify.h"
 
 using k3samd_kern::f4;
 
@@ -196,17 +197,9 @@ int mem_selftest(void* d_report) {
   if (mem_report_reset(d_report)) return 1;
   launch_mem_verify(0, buf, n_cells, 0, spec, d_report);
   HIP_CHECK(hipGetLastError());
-  HostMemReport r;
-  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-  int caught;
-  if (!drill_passed(r, flips, &caught)) {
-    std::printf("memtest selftest: FAIL (caught %d/3, bad_dwords %lld, "
-                "bad_bits %lld, xor_or 0x%08x)\n",
-                caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
-    return 3;
-  }
-  std::printf("memtest selftest: detector caught 3/3 injected flips\n");
-  return 0;
+  return drill_verdict(d_report, flips,
+                       {"memtest", "", "bad_dwords",
+                        "detector caught 3/3 injected flips"});
 }
 
 // Host-side pattern dump (no HIP call): one cell per line, d0..d3 as hex.
@@ -359,239 +352,88 @@ int gemm_operand_dump(char** a) {
   return 0;
 }
 
-// Element (m, n) of the generator product as a host integer dot product.
-long long gemm_host_dot(uint64_t seed, uint32_t m, uint32_t n, int64_t k) {
-  long long s = 0;
-  for (int64_t kk = 0; kk < k; ++kk)
-    s += (long long)k3samd_kern::gemm_operand(seed, 0, m, (uint32_t)kk) *
-         k3samd_kern::gemm_operand(seed, 1, (uint32_t)kk, n);
-  return s;
-}
-
-// The buffers of one M x N x K problem: bf16 A[M,K] and Bt[N,K], fp32 C
-// and gold, and the per-tile XCC_ID/HW_ID record.
-struct GemmBufs {
+// The bf16 problem of the driver in gemm_verify.h: bf16 A[M,K] and Bt[N,K]
+// of small integers from gemm_pattern.h.
+struct Bf16Problem {
+  static constexpr const char* kTag = "gemmtest";
+  static constexpr int64_t kSelftestK = 128;
   DevBuf<void> a, bt;
-  DevBuf<float> c, gold;
-  DevBuf<int> where;
-  int64_t tiles = 0;
+  int64_t m = 0, n = 0, k = 0;
 
-  int alloc(int64_t m, int64_t n, int64_t k) {
-    tiles = (m / k3samd_kern::kGemmBM) * (n / k3samd_kern::kGemmBN);
+  Bf16Problem fresh() const { return {}; }
+  const char* label() const { return ""; }
+  int alloc(int64_t m_, int64_t n_, int64_t k_) {
+    m = m_, n = n_, k = k_;
     HIP_CHECK(a.alloc((size_t)m * k * 2));
     HIP_CHECK(bt.alloc((size_t)n * k * 2));
-    HIP_CHECK(c.alloc((size_t)m * n * 4));
-    HIP_CHECK(gold.alloc((size_t)m * n * 4));
-    HIP_CHECK(where.alloc((size_t)tiles * 8));
-    HIP_CHECK(hipMemset(c, 0xFF, (size_t)m * n * 4));  // NaN: unwritten != gold
-    HIP_CHECK(hipMemset(where, 0xFF, (size_t)tiles * 8));
     return 0;
+  }
+  void fill(uint64_t seed) {
+    k3samd_kern::launch_gemm_fill(0, a, 0, seed, m, k);
+    k3samd_kern::launch_gemm_fill(0, bt, 1, seed, n, k);
+  }
+  void gemm(float* c, int* where) {
+    k3samd_kern::launch_gemm_bf16_nt(0, a, bt, c, where, m, n, k);
+  }
+  void ref(float* gold) {
+    k3samd_kern::launch_gemm_ref_int(0, a, bt, gold, m, n, k);
+  }
+
+  // Element (row, col) of the generator product as a host integer dot product.
+  float host_elem(uint64_t seed, uint32_t row, uint32_t col) const {
+    long long s = 0;
+    for (int64_t kk = 0; kk < k; ++kk)
+      s += (long long)k3samd_kern::gemm_operand(seed, 0, row, (uint32_t)kk) *
+           k3samd_kern::gemm_operand(seed, 1, (uint32_t)kk, col);
+    return (float)s;
+  }
+  // host operands once, then the integer product
+  std::vector<float> host_product(uint64_t seed) const {
+    using k3samd_kern::gemm_operand;
+    std::vector<int> ha(m * k), hb(k * n);
+    for (int64_t i = 0; i < m; ++i)
+      for (int64_t kk = 0; kk < k; ++kk)
+        ha[i * k + kk] = gemm_operand(seed, 0, (uint32_t)i, (uint32_t)kk);
+    for (int64_t kk = 0; kk < k; ++kk)
+      for (int64_t j = 0; j < n; ++j)
+        hb[kk * n + j] = gemm_operand(seed, 1, (uint32_t)kk, (uint32_t)j);
+    std::vector<float> c(m * n);
+    for (int64_t i = 0; i < m; ++i)
+      for (int64_t j = 0; j < n; ++j) {
+        int s = 0;
+        for (int64_t kk = 0; kk < k; ++kk) s += ha[i * k + kk] * hb[kk * n + j];
+        c[i * n + j] = (float)s;
+      }
+    return c;
+  }
+  void print_product_verdict(long long bad_mfma, long long bad_gold) const {
+    if (bad_mfma || bad_gold)
+      std::printf("gemmtest selftest: FAIL (256x256x128 vs host product: %lld "
+                  "MFMA element(s), %lld gold element(s) differ)\n",
+                  bad_mfma, bad_gold);
+    else
+      std::printf("gemmtest selftest: 256x256x128 MFMA product and integer "
+                  "gold match the host product exactly\n");
   }
 };
 
-// Self-test: (1) a 256x256x128 product, both the MFMA result and the
-// integer gold, against the host integer product of gemm_pattern.h;
-// (2) the detector drill on C against the gold.
-// Returns 0 ok, 3 failed, 1 HIP error.
-int gemm_selftest(void* d_report) {
-  using namespace k3samd_kern;
-  const int64_t m = 256, n = 256, k = 128;
-  const uint64_t seed = 0x5EEDF00Dull;
-  GemmBufs g;
-  if (g.alloc(m, n, k)) return 1;
-  launch_gemm_fill(0, g.a, 0, seed, m, k);
-  launch_gemm_fill(0, g.bt, 1, seed, n, k);
-  launch_gemm_ref_int(0, g.a, g.bt, g.gold, m, n, k);
-  launch_gemm_bf16_nt(0, g.a, g.bt, g.c, g.where, m, n, k);
-  HIP_CHECK(hipGetLastError());
-  std::vector<float> hc(m * n), hg(m * n);
-  HIP_CHECK(hipMemcpy(hc.data(), g.c, hc.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hg.data(), g.gold, hg.size() * 4, hipMemcpyDeviceToHost));
-  // host operands once, then the integer product
-  std::vector<int> ha(m * k), hb(k * n);
-  for (int64_t i = 0; i < m; ++i)
-    for (int64_t kk = 0; kk < k; ++kk)
-      ha[i * k + kk] = gemm_operand(seed, 0, (uint32_t)i, (uint32_t)kk);
-  for (int64_t kk = 0; kk < k; ++kk)
-    for (int64_t j = 0; j < n; ++j)
-      hb[kk * n + j] = gemm_operand(seed, 1, (uint32_t)kk, (uint32_t)j);
-  long long bad_mfma = 0, bad_gold = 0;
-  for (int64_t i = 0; i < m; ++i)
-    for (int64_t j = 0; j < n; ++j) {
-      int s = 0;
-      for (int64_t kk = 0; kk < k; ++kk) s += ha[i * k + kk] * hb[kk * n + j];
-      if (hc[i * n + j] != (float)s) ++bad_mfma;
-      if (hg[i * n + j] != (float)s) ++bad_gold;
-    }
-  if (bad_mfma || bad_gold) {
-    std::printf("gemmtest selftest: FAIL (256x256x128 vs host product: %lld "
-                "MFMA element(s), %lld gold element(s) differ)\n",
-                bad_mfma, bad_gold);
-    return 3;
-  }
-  std::printf("gemmtest selftest: 256x256x128 MFMA product and integer gold "
-              "match the host product exactly\n");
-
-  DrillFlip flips[3] = {{0, 0, 1u << 0},
-                        {12345, 0, 1u << 17},
-                        {(uint64_t)(m * n - 1), 0, 1u << 31}};
-  for (DrillFlip& f : flips) {
-    std::memcpy(&f.expect, &hg[f.index], 4);
-    if (mem_flip(g.c, f.index, f.mask)) return 1;
-  }
-  if (mem_report_reset(d_report)) return 1;
-  launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
-  HIP_CHECK(hipGetLastError());
-  HostMemReport r;
-  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-  int caught;
-  if (!drill_passed(r, flips, &caught)) {
-    std::printf("gemmtest selftest: FAIL (caught %d/3, bad_elems %lld, "
-                "bad_bits %lld, xor_or 0x%08x)\n",
-                caught, r.bad_dwords(), r.bad_bits(), r.xor_or());
-    return 3;
-  }
-  std::printf("gemmtest selftest: detector caught 3/3 injected flips\n");
-  return 0;
-}
-
 int run_gemmtest(const Options& o) {
-  using namespace k3samd_kern;
-  const int64_t m = o.gemm_m, n = o.gemm_n, k = o.gemm_k;
-  const int iters = o.gemm_iters, seconds = o.gemm_seconds,
-            inject = o.gemm_inject;
-  const uint64_t seed = 0;
-  DevBuf<long long> d_report;
-  HIP_CHECK(d_report.alloc(sizeof(long long) * kMemReportLen));
-  if (o.do_check) {
-    int rc = gemm_selftest(d_report);
-    if (rc) return rc;
-  }
-  GemmBufs g;
-  if (g.alloc(m, n, k)) return 1;
-  launch_gemm_fill(0, g.a, 0, seed, m, k);
-  launch_gemm_fill(0, g.bt, 1, seed, n, k);
-  float gold_ms;  // one timed launch, no warm-up
-  if (EventTimer().best_of(0, 1, [&](bool) {
-        launch_gemm_ref_int(0, g.a, g.bt, g.gold, m, n, k);
-      }, &gold_ms))
-    return 1;
-
-  // gold spot-check: 64 fixed elements against host integer dot products
-  // of the generator — independent of the device entirely
-  for (int i = 0; i < 64; ++i) {
-    const uint32_t row = i == 63 ? (uint32_t)(m - 1)
-                                 : (uint32_t)(((uint64_t)i * 0x9E3779B1ull) % (uint64_t)m);
-    const uint32_t col = i == 63 ? (uint32_t)(n - 1)
-                                 : (uint32_t)(((uint64_t)i * 0x85EBCA6Bull + 7) % (uint64_t)n);
-    float got;
-    HIP_CHECK(hipMemcpy(&got, g.gold + (size_t)row * n + col, 4,
-                        hipMemcpyDeviceToHost));
-    const long long want = gemm_host_dot(seed, row, col, k);
-    if (got != (float)want) {
-      std::printf("gemmtest: gold spot-check FAIL at [%u][%u]: device %.1f, "
-                  "host %lld\n", row, col, got, want);
-      return 3;
-    }
-  }
-  std::printf("gemmtest: %lldx%lldx%lld, gold by integer VALU in %.1f ms, "
-              "spot-check 64/64 vs host%s\n",
-              (long long)m, (long long)n, (long long)k, gold_ms,
-              inject ? " [fault injection ON]" : "");
-
-  ThermalSampler thermal;
-  if (mem_report_reset(d_report)) return 1;
-  const double flops_per = 2.0 * (double)m * (double)n * (double)k;
-  std::printf("%6s %10s %12s %6s %7s\n", "t(s)", "iters", "TFLOP/s", "temp",
-              "power");
-  long long done = 0, done_last = 0;
-  int batch = 1;
-  const auto t0 = Clock::now();
-  auto t_last = t0;
-  double next_report = 2.0;
-  auto status = [&] {
-    thermal.sample();
-    const double dt = seconds_since(t_last);
-    std::printf("%6.0f %10lld %12.1f %s\n", seconds_since(t0), done,
-                dt > 0 ? (done - done_last) * flops_per / dt / 1e12 : 0.0,
-                thermal.cells);
-    std::fflush(stdout);
-    done_last = done;
-    t_last = Clock::now();
-  };
-  while (seconds > 0 ? seconds_since(t0) < (double)seconds : done < iters) {
-    int todo = batch;
-    if (seconds <= 0 && todo > iters - done) todo = (int)(iters - done);
-    const auto tb = Clock::now();
-    for (int i = 0; i < todo; ++i) {
-      launch_gemm_bf16_nt(0, g.a, g.bt, g.c, g.where, m, n, k);
-      if (done == 0 && i == 0 && inject > 0) {
-        // operator alerting drill: N single-bit flips (bit f % 32) in the
-        // first result before its compare, at elements evenly spaced from 0
-        // as documented
-        const uint64_t step = (uint64_t)(m * n) / (uint64_t)inject;
-        HIP_CHECK(hipDeviceSynchronize());
-        for (int f = 0; f < inject; ++f)
-          if (mem_flip(g.c, (uint64_t)f * step, 1u << (f % 32))) return 1;
-      }
-      launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
-    }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    done += todo;
-    // size the batch to ~0.2 s between host syncs
-    const double per = seconds_since(tb) / todo;
-    batch = per > 0 ? (int)(0.2 / per) : 64;
-    if (batch < 1) batch = 1;
-    if (batch > 64) batch = 64;
-    if (seconds_since(t0) >= next_report) {
-      status();
-      next_report += 2.0;
-    }
-  }
-  const double total_s = seconds_since(t0);
-  if (done != done_last) status();  // the tail since the last line
-
-  HostMemReport r;
-  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
-  std::vector<int> where((size_t)g.tiles * 2);
-  HIP_CHECK(hipMemcpy(where.data(), g.where, where.size() * 4,
-                      hipMemcpyDeviceToHost));
-  auto xcc_of = [&](unsigned long long elem, unsigned* hw_id) {
-    const int64_t row = (int64_t)(elem / (uint64_t)n), col = (int64_t)(elem % (uint64_t)n);
-    const int64_t tile = (row / kGemmBM) * (n / kGemmBN) + col / kGemmBN;
-    if (hw_id) *hw_id = (unsigned)where[2 * tile + 1];
-    return where[2 * tile] & 0xF;
-  };
-  const bool clean = r.bad_dwords() == 0;
-  if (!clean) {
-    std::printf("gemmtest: MISCOMPARE - %lld element(s), %lld bit(s)\n",
-                r.bad_dwords(), r.bad_bits());
-    for (int i = 0; i < r.n_log(); ++i) {
-      const long long* rec = r.log(i);
-      unsigned hw_id = 0;
-      const int xcc = xcc_of((unsigned long long)rec[0], &hw_id);
-      std::printf("C[%llu][%llu] expected 0x%08x actual 0x%08x xor 0x%08x "
-                  "xcc %d hw_id 0x%08x\n",
-                  (unsigned long long)rec[0] / (unsigned long long)n,
-                  (unsigned long long)rec[0] % (unsigned long long)n,
-                  (unsigned)rec[1], (unsigned)rec[2],
-                  (unsigned)(rec[1] ^ rec[2]), xcc, hw_id);
-    }
-  }
+  Bf16Problem p;
+  GemmVerifyResult v;
+  int rc = gemm_verify(p, o.gemm_m, o.gemm_n, o.gemm_k, o.gemm_iters,
+                       o.gemm_seconds, o.gemm_inject, o.do_check, &v);
+  if (rc) return rc;
   std::printf(
       "{\"payload\": \"mi-gemmtest\", \"m\": %lld, \"n\": %lld, \"k\": %lld, "
       "\"iters\": %lld, \"bad_elems\": %lld, \"bad_bits\": %lld, "
       "\"first_bad_row\": %lld, \"first_bad_col\": %lld, "
       "\"first_bad_xcc\": %d, \"avg_tflops\": %.1f, \"gold_ms\": %.1f, "
       "\"max_temp_c\": %ld, \"max_power_w\": %.0f, \"compute_clean\": %s}\n",
-      (long long)m, (long long)n, (long long)k, done, r.bad_dwords(),
-      r.bad_bits(), clean ? -1LL : (long long)(r.first() / (uint64_t)n),
-      clean ? -1LL : (long long)(r.first() % (uint64_t)n),
-      clean ? -1 : xcc_of(r.first(), nullptr),
-      done * flops_per / total_s / 1e12, gold_ms, thermal.max_temp_c,
-      thermal.max_power_w, clean ? "true" : "false");
-  return clean ? 0 : 4;
+      (long long)o.gemm_m, (long long)o.gemm_n, (long long)o.gemm_k, v.iters,
+      v.report.bad_dwords(), v.report.bad_bits(), v.first_bad_row,
+      v.first_bad_col, v.first_bad_xcc,
+      v.tflops(o.gemm_m, o.gemm_n, o.gemm_k), v.gold_ms, v.max_temp_c, v.max_power_w, v.clean() ? "true" : "false");
+  return v.clean() ? 0 : 4;
 }
 
 // ---- STREAM modes ----
@@ -797,10 +639,6 @@ int run_burn(const Options& o, StreamBufs& s) {
   return 0;
 }
 
-const char* gpu_name(const hipDeviceProp_t& prop) {
-  return prop.name[0] ? prop.name : "AMD GPU";  // some boxes report no name
-}
-
 // Default mode: the STREAM table (2 warm-ups, best of --iters per cell),
 // the MFMA rows (1 warm-up at 256 iterations, best of 3: rides out the
 // clock ramp) and the JSON line.
@@ -867,7 +705,7 @@ int run_stream_table(const Options& o, StreamBufs& s,
       "{\"payload\": \"mi-stream\", \"gpu\": \"%s\", \"arch\": \"%s\", "
       "\"buffer_MiB\": %lld, \"triad_gbps\": %.1f, \"mfma_bf16_tflops\": "
       "%.1f}\n",
-      gpu_name(prop), prop.gcnArchName, (long long)o.mib,
+      prop.name, prop.gcnArchName, (long long)o.mib,
       gbps(triad.bytes, std::min(triad.best_ms[0], triad.best_ms[1])),
       mfma_tf);
   return 0;
@@ -875,16 +713,22 @@ int run_stream_table(const Options& o, StreamBufs& s,
 
 // ---- command line ----
 
-constexpr int kRun = -1;  // parse_options: no exit status yet, go on
+const char kUsage[] =
+    "mi-stream [--mib N] [--iters N] [--device D] [--no-mfma]"
+    " [--tune] [--lds-compare] [--all-gpus] [--burn SECONDS]"
+    " [--memtest [--passes N] [--vram-percent P]"
+    " [--memtest-inject N]] [--memtest-pattern-dump PATTERN"
+    " SEED INVERT CELL_OFFSET N_CELLS]"
+    " [--gemmtest [--gemm-size S | --gemm-mnk M N K]"
+    " [--gemm-iters I | --gemm-seconds T] [--gemm-inject N]]"
+    " [--gemm-operand-dump WHICH SEED ROW0 COL0 ROWS COLS]\n";
 
 // Flags are matched left to right. The two dump flags run (host only) and
 // return as soon as they are reached; an unknown flag, or a flag short of
 // its values, prints the usage line and returns 2 (--help: 0).
 int parse_options(int argc, char** argv, Options& o) {
   for (int i = 1; i < argc; ++i) {
-    auto flag = [&](const char* name, int n_values = 0) {
-      return !std::strcmp(argv[i], name) && i + n_values < argc;
-    };
+    const FlagMatcher flag{argc, argv, i};
     if (flag("--mib", 1)) o.mib = std::atoll(argv[++i]);
     else if (flag("--iters", 1)) o.iters = std::atoi(argv[++i]);
     else if (flag("--device", 1)) o.device = std::atoi(argv[++i]);
@@ -912,17 +756,7 @@ int parse_options(int argc, char** argv, Options& o) {
     else if (flag("--gemm-inject", 1)) o.gemm_inject = std::atoi(argv[++i]);
     else if (flag("--gemm-operand-dump", 6))
       return gemm_operand_dump(argv + i + 1);
-    else {
-      std::printf("mi-stream [--mib N] [--iters N] [--device D] [--no-mfma]"
-                  " [--tune] [--lds-compare] [--all-gpus] [--burn SECONDS]"
-                  " [--memtest [--passes N] [--vram-percent P]"
-                  " [--memtest-inject N]] [--memtest-pattern-dump PATTERN"
-                  " SEED INVERT CELL_OFFSET N_CELLS]"
-                  " [--gemmtest [--gemm-size S | --gemm-mnk M N K]"
-                  " [--gemm-iters I | --gemm-seconds T] [--gemm-inject N]]"
-                  " [--gemm-operand-dump WHICH SEED ROW0 COL0 ROWS COLS]\n");
-      return !std::strcmp(argv[i], "--help") ? 0 : 2;
-    }
+    else return usage_status(kUsage, argv[i]);
   }
   return kRun;
 }
@@ -953,16 +787,6 @@ int validate_options(Options& o) {
   return 0;
 }
 
-int print_banner(int device, int ndev, hipDeviceProp_t* prop) {
-  HIP_CHECK(hipSetDevice(device));
-  HIP_CHECK(hipGetDeviceProperties(prop, device));
-  std::printf("mi-stream: %s (%s), %d visible GPU(s), %d CUs, %.0f GiB VRAM\n",
-              gpu_name(*prop), prop->gcnArchName, ndev,
-              prop->multiProcessorCount,
-              (double)prop->totalGlobalMem / (1 << 30));
-  return 0;
-}
-
 }  // namespace
 
 // Exit status: 0 ok, 1 HIP error, 2 usage, 3 an oracle/self-test failed,
@@ -973,12 +797,10 @@ int main(int argc, char** argv) {
   if (rc != kRun) return rc;
   if ((rc = validate_options(o)) != 0) return rc;
 
+  // --all-gpus counts the devices and selects none here
   int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (ndev == 0) {
-    std::fprintf(stderr, "mi-stream: no GPUs visible\n");
-    return 1;
-  }
+  hipDeviceProp_t prop;
+  if (open_device(o.device, &ndev, o.all_gpus ? nullptr : &prop)) return 1;
 
   // When several mode flags are given, the first in this order wins:
   // all-gpus, memtest, gemmtest, lds-compare, tune, burn, then the default
@@ -988,8 +810,9 @@ int main(int argc, char** argv) {
     return run_all_gpus(o, ndev);
   }
 
-  hipDeviceProp_t prop;
-  if (print_banner(o.device, ndev, &prop)) return 1;
+  std::printf("mi-stream: %s (%s), %d visible GPU(s), %d CUs, %.0f GiB VRAM\n",
+              prop.name, prop.gcnArchName, ndev, prop.multiProcessorCount,
+              (double)prop.totalGlobalMem / (1 << 30));
   // these two run their own self-tests (unless --no-check)
   if (o.memtest) return run_memtest(o);
   if (o.gemmtest) return run_gemmtest(o);

@@ -1,8 +1,11 @@
-// Pieces the GPU payload programs (mi-stream, mi-mxgemm, mi-cutest, mi-hostlink) share: the HIP
-// error macro, an owning device buffer, event timing, sysfs thermal
+// Pieces the GPU payload programs (mi-stream, mi-mxgemm, mi-cutest,
+// mi-hostlink) share: the HIP error macro, the command-line flag matcher,
+// the device opener, an owning device buffer, event timing, sysfs thermal
 // sampling, and the host side of the memtest / gemmtest report with its
-// detector drill. Each payload is one translation unit, so everything here
-// sits in an unnamed namespace.
+// detector drill and the drill's verdict lines. The verified-GEMM driver of
+// mi-stream --gemmtest and mi-mxgemm builds on these in gemm_verify.h. Each
+// payload is one translation unit, so everything here sits in an unnamed
+// namespace.
 //
 // Define K3_PAYLOAD_NAME (the program's name as a string literal, the prefix
 // of its error messages) before including this header.
@@ -19,6 +22,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <utility>
 
 #include "../../k3samd/ops/hip/memtest_kernels.h"
@@ -36,6 +40,45 @@
   } while (0)
 
 namespace {
+
+// ---- command line ----
+
+constexpr int kRun = -1;  // parse_options: no exit status yet, go on
+
+// flag(name, n): argv[i] is `name` and n more arguments follow it, so a flag
+// short of its values matches nothing and falls through to the usage text.
+struct FlagMatcher {
+  int argc;
+  char** argv;
+  int i;
+  bool operator()(const char* name, int n_values = 0) const {
+    return !std::strcmp(argv[i], name) && i + n_values < argc;
+  }
+};
+
+// What no flag matched: print the usage text; --help is status 0, else 2.
+int usage_status(const char* usage, const char* arg) {
+  std::printf("%s", usage);
+  return !std::strcmp(arg, "--help") ? 0 : 2;
+}
+
+// ---- device ----
+
+// Count the visible GPUs into *ndev (none is an error). With `prop`, also
+// select `device` and read its properties, an empty name (some boxes report
+// none) replaced by "AMD GPU"; without, no device is selected.
+int open_device(int device, int* ndev, hipDeviceProp_t* prop) {
+  HIP_CHECK(hipGetDeviceCount(ndev));
+  if (*ndev == 0) {
+    std::fprintf(stderr, K3_PAYLOAD_NAME ": no GPUs visible\n");
+    return 1;
+  }
+  if (!prop) return 0;
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipGetDeviceProperties(prop, device));
+  if (!prop->name[0]) std::strcpy(prop->name, "AMD GPU");
+  return 0;
+}
 
 using Clock = std::chrono::steady_clock;
 double seconds_since(Clock::time_point t) {
@@ -167,6 +210,41 @@ bool drill_passed(const HostMemReport& r, const DrillFlip (&flips)[3],
   return *caught == 3 && r.bad_dwords() == 3 && r.bad_bits() == 3 &&
          r.first() == flips[0].index && r.v[4] == 3 &&
          r.xor_or() == (flips[0].mask | flips[1].mask | flips[2].mask);
+}
+
+// The tail every drill shares. `words` are the program's tag, the drill's
+// name with a trailing space (or ""), the unit of the report's count and the
+// success sentence: "<tag> selftest: FAIL (<drill>caught c/3, <unit> ...)"
+// and status 3, or "<tag> selftest: <ok>" and 0.
+struct DrillWords {
+  const char *tag, *drill, *unit, *ok;
+};
+
+int drill_verdict(const HostMemReport& r, const DrillFlip (&flips)[3],
+                  const DrillWords& w) {
+  int caught;
+  if (!drill_passed(r, flips, &caught)) {
+    std::printf("%s selftest: FAIL (%scaught %d/3, %s %lld, bad_bits %lld, "
+                "xor_or 0x%08x)\n",
+                w.tag, w.drill, caught, w.unit, r.bad_dwords(), r.bad_bits(),
+                r.xor_or());
+    return 3;
+  }
+  std::printf("%s selftest: %s\n", w.tag, w.ok);
+  return 0;
+}
+
+int mem_report_download(HostMemReport& r, const void* d_report) {
+  HIP_CHECK(hipMemcpy(r.v, d_report, sizeof(r.v), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The same on a device report, downloaded first (1 on a HIP error).
+int drill_verdict(const void* d_report, const DrillFlip (&flips)[3],
+                  const DrillWords& w) {
+  HostMemReport r;
+  if (mem_report_download(r, d_report)) return 1;
+  return drill_verdict(r, flips, w);
 }
 
 }  // namespace

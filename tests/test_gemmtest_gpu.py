@@ -359,6 +359,13 @@ def test_mi_stream_gemmtest_clean():
     assert j["bad_elems"] == 0 and j["bad_bits"] == 0
     assert (j["first_bad_row"], j["first_bad_col"], j["first_bad_xcc"]) == \
         (-1, -1, -1)
+    # the member order log parsers see
+    pairs = json.loads(proc.stdout.strip().splitlines()[-1],
+                       object_pairs_hook=list)
+    assert [key for key, _ in pairs] == [
+        "payload", "m", "n", "k", "iters", "bad_elems", "bad_bits",
+        "first_bad_row", "first_bad_col", "first_bad_xcc", "avg_tflops",
+        "gold_ms", "max_temp_c", "max_power_w", "compute_clean"]
 
 
 def test_mi_stream_gemmtest_inject():

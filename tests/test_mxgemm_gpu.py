@@ -365,6 +365,14 @@ def test_mi_mxgemm_clean(fmt):
     assert (j["first_bad_row"], j["first_bad_col"], j["first_bad_xcc"]) == \
         (-1, -1, -1)
     assert isinstance(j["tflops"], float) and j["tflops"] > 0
+    # the member order log parsers see
+    pairs = json.loads(proc.stdout.strip().splitlines()[-1],
+                       object_pairs_hook=list)
+    assert [key for key, _ in pairs] == [
+        "payload", "format", "m", "n", "k", "iters", "tflops",
+        "compute_clean", "bad_elems", "bad_bits", "first_bad_row",
+        "first_bad_col", "first_bad_xcc", "gold_ms", "max_temp_c",
+        "max_power_w"]
 
 
 @pytest.mark.parametrize("fmt", ["fp8", "fp4"])
