@@ -1,8 +1,9 @@
-// Per-CU self-test: geometry, the decode of the placement registers, and the
-// VALU signature as a pure function. One source of truth for the device
-// kernels (cu_test_kernels.h) and for host code (mi-cutest's signature dump
-// and self-test, the torch binding's cu_signature_expected) — no HIP
-// include, so a plain host compiler can use it.
+// Per-CU self-test: geometry, the placement registers (ids, the record
+// every kernel writes, the decode), and the VALU signature as a pure
+// function. One source of truth for the device kernels (cu_test_kernels.h,
+// the GEMM kernels' placement record) and for host code (mi-cutest's
+// signature dump and self-test, the torch binding's cu_signature_expected)
+// — no HIP include, so a plain host compiler can use it.
 //
 // Placement. s_getreg HW_ID, gfx9-family layout:
 //   WAVE_ID 3:0 | SIMD_ID 5:4 | PIPE_ID 7:6 | CU_ID 11:8 | SH_ID 12 |
@@ -77,7 +78,21 @@ constexpr int kCuMaxInject = 256;                // inject list rows per launch
 // cross-wave LDS fold): the lane's cell index with this bit set.
 constexpr uint64_t kCuFoldCellBit = 1ull << 40;
 
-// ---- placement decode ----
+// ---- placement: the registers, the record, the decode ----
+
+// s_getreg_b32 operand: id | offset << 6 | (width - 1) << 11, full 32 bits
+constexpr int kHwRegHwId = 4 | (31 << 11);
+constexpr int kHwRegXccId = 20 | (31 << 11);
+
+#if defined(__HIPCC__)
+// where[slot] = {XCC_ID, HW_ID} of the calling wave; the caller picks the
+// lane that writes. (__forceinline__ is a HIP-header macro: spelled out.)
+__device__ inline __attribute__((always_inline)) void cu_record_placement(
+    int* where, int slot) {
+  where[2 * slot] = (int)__builtin_amdgcn_s_getreg(kHwRegXccId);
+  where[2 * slot + 1] = (int)__builtin_amdgcn_s_getreg(kHwRegHwId);
+}
+#endif
 
 K3_CU_HD inline uint32_t cu_simd(uint32_t hw_id) { return (hw_id >> 4) & 3u; }
 K3_CU_HD inline uint32_t cu_cu(uint32_t hw_id) { return (hw_id >> 8) & 15u; }

@@ -57,7 +57,6 @@
 #include <cstdint>
 
 #include "cu_pattern.h"
-#include "gemm_kernels.h"
 #include "memtest_kernels.h"
 
 namespace k3samd_kern {
@@ -101,10 +100,7 @@ __global__ __launch_bounds__(kCuWgThreads) void cu_lds_march_kernel(
   const int wg = blockIdx.x;
   const uint64_t base = (uint64_t)wg * kCuLdsCells;
 
-  if (tid == 0) {
-    where[2 * wg] = (int)__builtin_amdgcn_s_getreg(kHwRegXccId);
-    where[2 * wg + 1] = (int)__builtin_amdgcn_s_getreg(kHwRegHwId);
-  }
+  if (tid == 0) cu_record_placement(where, wg);
 
   // after the write of phase `ph` of pass 0 (workgroup-uniform control flow)
   auto plant = [&](int ph) {
@@ -163,10 +159,7 @@ __global__ __launch_bounds__(kCuWgThreads) void cu_valu_signature_kernel(
   const int wg = blockIdx.x;
   const int slot = wg * kCuWaves + wave;
 
-  if (lane == 0) {
-    where[2 * slot] = (int)__builtin_amdgcn_s_getreg(kHwRegXccId);
-    where[2 * slot + 1] = (int)__builtin_amdgcn_s_getreg(kHwRegHwId);
-  }
+  if (lane == 0) cu_record_placement(where, slot);
 
   CuSigState st = cu_sig_init(seed, (uint32_t)lane);
   for (int r = 0; r < rounds; ++r) {

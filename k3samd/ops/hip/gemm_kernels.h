@@ -13,28 +13,35 @@
 // With gemm_pattern.h's small-integer operands the fp32 result is exact
 // and unique (see the bound there), so C is compared BITWISE against gold.
 //
-// gemm_bf16_nt_kernel, shape contract M % 128 == N % 128 == K % 64 == 0
-// (checked on the host; no edge handling in the kernel):
-//   * 128x128 block tile, BK = 64, 256 threads = 2x2 waves, each wave a
-//     64x64 sub-tile held as acc[4][4] of f32x4 (v_mfma_f32_16x16x32_bf16;
-//     lane l holds A[l&15][(l>>4)*8+j], C col = lane&15, row =
-//     (lane>>4)*4+reg — the layout validated by mfma_gemm16_kernel).
-//   * Both operand tiles are [128 rows][64 bf16] = 128-byte rows, staged
-//     by global_load_lds width 16: one wave instruction writes 1 KiB =
-//     8 whole rows, LDS destination lane-linear.
+// Tile geometry of gemm_bf16_nt_kernel and mx_gemm_nt_kernel<0|4>
+// (mx_gemm_kernels.h), stated once in GemmTile and the gemm_* helpers. It
+// is a geometry of BYTES: one K-step is kGemmStepBytes = 128 bytes of every
+// operand row = 64 bf16 (kGemmBK), 128 fp8 or 256 fp4. Shape contract
+// M % 128 == N % 128 == 0, K whole steps (host-checked; no edge handling):
+//   * 128x128 block tile, 256 threads = 2x2 waves, each wave a 64x64
+//     sub-tile held as acc[4][4] of f32x4 (16x16 MFMAs: lane l holds row /
+//     column l&15 of its fragment, k-group l>>4; C/D as mfma_tile16_index).
+//   * Both operand tiles are [128 rows][128 bytes], staged by
+//     global_load_lds width 16: one wave instruction writes 1 KiB = 8 whole
+//     rows, LDS destination lane-linear; instruction i (0..3) of wave `wid`
+//     fills rows (i*4 + wid)*8 .. +7, lane l row +(l>>3), chunk slot l&7.
 //   * LDS swizzle: a linear image would put the 16 rows a ds_read_b128
-//     lane group reads on two 16-byte slots of the 256-byte bank row
-//     (8-way conflict). Chunk c of row r is kept at chunk slot
-//     c ^ ((r >> 1) & 7): with r & 1 selecting the half of the bank row,
-//     16 consecutive rows then cover all 16 slots. The XOR is applied to
-//     the per-lane SOURCE address of the staging load and to the fragment
-//     read address — the same involution on both sides; the LDS
-//     destination itself stays linear, as global_load_lds requires.
+//     lane group reads on two 16-byte slots of the 256-byte bank row (8-way
+//     conflict). Chunk c of row r is kept at chunk slot c ^ ((r >> 1) & 7):
+//     with r & 1 selecting the half of the bank row, 16 consecutive rows
+//     then cover all 16 slots. The XOR is applied to the per-lane SOURCE
+//     address of the staging load (i only adds multiples of 32 to the row,
+//     so one schunk serves all four) and to the fragment read address (fsw:
+//     sub-tile bases are multiples of 16, so it depends on the lane alone)
+//     — the same involution on both sides; the LDS destination stays
+//     linear, as global_load_lds requires.
 //   * One __shared__ array, two plain __syncthreads() per K-step (the
 //     first drains the in-flight staging loads before anyone reads).
 //   * Flat grid, tile = blockIdx.x, row-major over (M/128, N/128).
-//   * where[tile] = {XCC_ID, HW_ID} hardware registers of the workgroup's
-//     first wave, so a bad tile can be attributed to an XCD / CU.
+//   * where[tile] = {XCC_ID, HW_ID} of the first wave: names the XCD / CU.
+// Each kernel keeps its fragment to itself: which chunks a lane reads, the
+// MFMA, the MX scale loads. bf16 (v_mfma_f32_16x16x32_bf16, two per step):
+// chunk s*4 + (l>>4) for MFMA s, the layout validated by mfma_gemm16_kernel.
 
 #pragma once
 
@@ -42,19 +49,20 @@
 
 #include <cstdint>
 
+#include "cu_pattern.h"
 #include "gemm_pattern.h"
 #include "memtest_kernels.h"
 #include "stream_kernels.h"
 
 namespace k3samd_kern {
 
-constexpr int kGemmBM = 128, kGemmBN = 128, kGemmBK = 64;
-constexpr int kGemmTileBytes = kGemmBM * kGemmBK * 2;  // 16 KiB per operand
-constexpr int kGemmRefTile = 64;                       // gold: 64x64 per block
-
-// s_getreg_b32 operand: id | offset << 6 | (width - 1) << 11, full 32 bits
-constexpr int kHwRegHwId = 4 | (31 << 11);
-constexpr int kHwRegXccId = 20 | (31 << 11);
+constexpr int kGemmBM = 128, kGemmBN = 128;
+constexpr int kGemmBK = 64;          // bf16 elements per K-step (host contract)
+constexpr int kGemmStepBytes = 128;  // row bytes per K-step, every format
+constexpr int kGemmTileBytes = kGemmBM * kGemmStepBytes;  // 16 KiB per operand
+constexpr int kGemmFragBytes = 16 * kGemmStepBytes;  // 16 rows: one fragment
+constexpr int kGemmRefTile = 64;     // gold: 64x64 per block
+static_assert(kGemmBK * 2 == kGemmStepBytes);
 
 // One 16-byte cell = 8 consecutive bf16 of one stored row. `cols8` is the
 // stored row length / 8. which = 0: stored [row = m][col = k] holds
@@ -84,6 +92,72 @@ __global__ void gemm_fill_kernel(u4* __restrict__ p, int64_t n_cells,
   p[i] = v;
 }
 
+#if K3_HAS_MFMA  // ---- the tile geometry (see the top of this file) ----
+// Chunk slot of 16-byte chunk `chunk` of tile row `row`; an involution.
+__device__ __forceinline__ int gemm_swizzle(int chunk, int row) {
+  return chunk ^ ((row >> 1) & 7);
+}
+
+// Where this thread stands in its workgroup's 128x128 tile.
+struct GemmTile {
+  int wid, tile;       // wave in the workgroup, tile = blockIdx.x
+  int64_t brow, bcol;  // first row / column of the tile in C
+  int srow, schunk;    // staging: tile row (of instruction 0), SOURCE chunk
+  int wr, wc;          // the wave's 64x64 sub-tile
+  int fr, fq, fsw;     // fragment row and k-group of this lane; chunk c of
+                       // its rows is read at slot c ^ fsw
+};
+
+__device__ __forceinline__ GemmTile gemm_tile(int tiles_n) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  GemmTile t;
+  t.wid = tid >> 6, t.tile = blockIdx.x;
+  t.brow = (int64_t)(t.tile / tiles_n) * kGemmBM;
+  t.bcol = (int64_t)(t.tile % tiles_n) * kGemmBN;
+  t.srow = t.wid * 8 + (lane >> 3), t.schunk = gemm_swizzle(lane & 7, t.srow);
+  t.wr = t.wid >> 1, t.wc = t.wid & 1;
+  t.fr = lane & 15, t.fq = lane >> 4, t.fsw = gemm_swizzle(0, t.fr);
+  return t;
+}
+
+// This lane's staging source at K-step 0; the tile starts at row `row0`.
+__device__ __forceinline__ const unsigned char* gemm_stage_src(
+    const void* base, int64_t row0, int row_bytes, const GemmTile& t) {
+  return static_cast<const unsigned char*>(base) +
+         (row0 + t.srow) * (int64_t)row_bytes + t.schunk * 16;
+}
+
+// One K-step of both tiles: gemm_stage_src() advanced to the step.
+__device__ __forceinline__ void gemm_stage(
+    const unsigned char* a_src, const unsigned char* b_src,
+    int64_t step32_bytes, unsigned char* lds_a, unsigned char* lds_b, int wid) {
+  using global_ptr = const __attribute__((address_space(1))) void*;
+  using lds_ptr = __attribute__((address_space(3))) void*;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int dst = (i * 4 + wid) * 1024;  // wave-uniform
+    __builtin_amdgcn_global_load_lds((global_ptr)(a_src + i * step32_bytes),
+                                     (lds_ptr)(lds_a + dst), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((global_ptr)(b_src + i * step32_bytes),
+                                     (lds_ptr)(lds_b + dst), 16, 0, 0);
+  }
+}
+
+// acc[m][n] is the 16x16 block (m, n) of the wave's sub-tile.
+__device__ __forceinline__ void gemm_store_acc(
+    float* __restrict__ C, int N, const GemmTile& t, const f32x4 (&acc)[4][4]) {
+  float* c_wave = C + (t.brow + t.wr * 64 + t.fq * 4) * (int64_t)N + t.bcol +
+                  t.wc * 64 + t.fr;
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        c_wave[(m * 16 + j) * (int64_t)N + n * 16] = acc[m][n][j];
+}
+#endif
+
 // launch bounds (256, 2): with a 512-register budget the compiler keeps the
 // accumulators in AGPRs and shuffles ~160 of them per K-step; capped at
 // 256 it uses the VGPR form of the MFMA (122 VGPRs, no copies).
@@ -96,63 +170,30 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(
   unsigned char* const lds_a = lds;
   unsigned char* const lds_b = lds + kGemmTileBytes;
 
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int tile = blockIdx.x;
-  const int64_t brow = (int64_t)(tile / tiles_n) * kGemmBM;
-  const int64_t bcol = (int64_t)(tile % tiles_n) * kGemmBN;
+  const GemmTile t = gemm_tile(tiles_n);
+  if (where != nullptr && threadIdx.x == 0) cu_record_placement(where, t.tile);
 
-  if (where != nullptr && tid == 0) {
-    where[2 * tile] = (int)__builtin_amdgcn_s_getreg(kHwRegXccId);
-    where[2 * tile + 1] = (int)__builtin_amdgcn_s_getreg(kHwRegHwId);
-  }
-
-  // Staging: instruction i (0..3) of wave `wid` fills tile rows
-  // (i*4 + wid)*8 .. +7; lane l lands on row +(l>>3), chunk slot l&7, and
-  // fetches source chunk slot ^ ((row >> 1) & 7). i only adds multiples
-  // of 32 to the row, so the XOR term is the same for all four.
-  const int srow = wid * 8 + (lane >> 3);
-  const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
-  const uint16_t* a_src = A + (brow + srow) * (int64_t)K + schunk * 8;
-  const uint16_t* b_src = Bt + (bcol + srow) * (int64_t)K + schunk * 8;
-  const int64_t step32 = 32 * (int64_t)K;  // 32 rows further down
-
-  // Fragment reads: row = sub-tile base + m*16 + (lane&15), k-chunk =
-  // s*4 + (lane>>4); bases are multiples of 16, so the XOR term depends
-  // on the lane alone.
-  const int wr = wid >> 1, wc = wid & 1;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int fsw = (fr >> 1) & 7;
-  const unsigned char* a_rd = lds_a + (wr * 64 + fr) * 128;
-  const unsigned char* b_rd = lds_b + (wc * 64 + fr) * 128;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int KB = 2 * K;  // bytes per stored row
+  const unsigned char* a_src = gemm_stage_src(A, t.brow, KB, t);
+  const unsigned char* b_src = gemm_stage_src(Bt, t.bcol, KB, t);
+  const int64_t step32 = 32 * (int64_t)KB;  // 32 rows further down
+  const unsigned char* a_rd = lds_a + (t.wr * 64 + t.fr) * kGemmStepBytes;
+  const unsigned char* b_rd = lds_b + (t.wc * 64 + t.fr) * kGemmStepBytes;
+  f32x4 acc[4][4] = {};
 
   for (int k0 = 0; k0 < K; k0 += kGemmBK) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int dst = (i * 4 + wid) * 1024;  // wave-uniform
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(a_src + i * step32 + k0),
-          (__attribute__((address_space(3))) void*)(lds_a + dst), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(b_src + i * step32 + k0),
-          (__attribute__((address_space(3))) void*)(lds_b + dst), 16, 0, 0);
-    }
+    gemm_stage(a_src + 2 * k0, b_src + 2 * k0, step32, lds_a, lds_b, t.wid);
     __syncthreads();  // drains the staging loads (vmcnt(0)), then barrier
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int coff = ((s * 4 + fq) ^ fsw) << 4;
+      const int coff = ((s * 4 + t.fq) ^ t.fsw) << 4;
       bf16x8 af[4], bfr[4];
 #pragma unroll
       for (int m = 0; m < 4; ++m)
-        af[m] = *reinterpret_cast<const bf16x8*>(a_rd + m * 16 * 128 + coff);
+        af[m] = *reinterpret_cast<const bf16x8*>(a_rd + m * kGemmFragBytes + coff);
 #pragma unroll
       for (int n = 0; n < 4; ++n)
-        bfr[n] = *reinterpret_cast<const bf16x8*>(b_rd + n * 16 * 128 + coff);
+        bfr[n] = *reinterpret_cast<const bf16x8*>(b_rd + n * kGemmFragBytes + coff);
 #pragma unroll
       for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -162,15 +203,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(
     }
     __syncthreads();  // everyone is done reading before the next stage
   }
-
-  float* c_wave = C + (brow + wr * 64 + fq * 4) * (int64_t)N + bcol + wc * 64 + fr;
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        c_wave[(m * 16 + j) * (int64_t)N + n * 16] = acc[m][n][j];
+  gemm_store_acc(C, N, t, acc);
 #else
   (void)A; (void)Bt; (void)C; (void)where; (void)K; (void)N; (void)tiles_n;
 #endif
@@ -200,10 +233,40 @@ __device__ __forceinline__ int gemm_dot4_i8(int a, int b, int c) {
 #endif
 }
 
-// Independent reference: 64x64 outputs per 256-thread block, 4x4 per
-// thread, operands converted to int8 and packed four-along-k in LDS
-// (rows padded to 17 words so the strided row reads spread over the
-// banks), int32 accumulation. No matrix-pipe instruction.
+// Shared by the gold kernels (this file's and mx_gemm_ref_int_kernel): 64x64
+// outputs per block, 4x4 per thread; `as` / `bs` hold 64 k of 64 rows as 16
+// words of four packed int8 (+1 pad word against bank conflicts). Word kw:
+__device__ __forceinline__ void gemm_ref_dot_word(
+    const int (&as)[kGemmRefTile][17], const int (&bs)[kGemmRefTile][17],
+    int tx, int ty, int kw, int (&acc)[4][4]) {
+  int a[4], b[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = as[ty * 4 + i][kw];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) b[j] = bs[tx * 4 + j][kw];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = gemm_dot4_i8(a[i], b[j], acc[i][j]);
+}
+
+// The accumulators count units of 1 / kUnitDenom (a power of two).
+template <int kUnitDenom>
+__device__ __forceinline__ void gemm_ref_store(
+    float* gold, int N, int64_t brow, int64_t bcol, int tx, int ty,
+    const int (&acc)[4][4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f4 v = {(float)acc[i][0], (float)acc[i][1], (float)acc[i][2],
+            (float)acc[i][3]};
+    if constexpr (kUnitDenom != 1) v *= 1.0f / kUnitDenom;
+    *reinterpret_cast<f4*>(gold + (brow + ty * 4 + i) * (int64_t)N + bcol +
+                           tx * 4) = v;
+  }
+}
+
+// Independent reference: operands converted to int8 and packed
+// four-along-k in LDS, int32 accumulation. No matrix-pipe instruction.
 __global__ __launch_bounds__(256) void gemm_ref_int_kernel(
     const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bt,
     float* __restrict__ gold, int K, int N, int tiles_n) {
@@ -213,12 +276,7 @@ __global__ __launch_bounds__(256) void gemm_ref_int_kernel(
   const int64_t brow = (int64_t)(blockIdx.x / tiles_n) * kGemmRefTile;
   const int64_t bcol = (int64_t)(blockIdx.x % tiles_n) * kGemmRefTile;
 
-  int acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0;
-
+  int acc[4][4] = {};
   for (int k0 = 0; k0 < K; k0 += 64) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -235,26 +293,10 @@ __global__ __launch_bounds__(256) void gemm_ref_int_kernel(
     }
     __syncthreads();
 #pragma unroll
-    for (int kw = 0; kw < 16; ++kw) {
-      int a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = as[ty * 4 + i][kw];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = bs[tx * 4 + j][kw];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = gemm_dot4_i8(a[i], b[j], acc[i][j]);
-    }
+    for (int kw = 0; kw < 16; ++kw) gemm_ref_dot_word(as, bs, tx, ty, kw, acc);
     __syncthreads();
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f4 v = {(float)acc[i][0], (float)acc[i][1], (float)acc[i][2],
-            (float)acc[i][3]};
-    *reinterpret_cast<f4*>(gold + (brow + ty * 4 + i) * (int64_t)N + bcol +
-                           tx * 4) = v;
-  }
+  gemm_ref_store<1>(gold, N, brow, bcol, tx, ty, acc);
 }
 
 // Streaming bitwise compare of two equally sized buffers, one 16-byte cell
@@ -278,11 +320,23 @@ __global__ void buf_compare_kernel(const u4* __restrict__ p,
 
 // ---- host-side launchers (no sync, errors via hipGetLastError) ----
 
+// The M / N half of every format's shape contract.
+inline bool gemm_grid_ok(int64_t m, int64_t n) {
+  return m > 0 && n > 0 && m % kGemmBM == 0 && n % kGemmBN == 0 &&
+         m <= (1 << 24) && n <= (1 << 24) &&
+         (m / kGemmBM) * (n / kGemmBN) <= (1 << 22);
+}
+
 // True when (m, n, k) meets gemm_bf16_nt_kernel's shape contract.
 inline bool gemm_shape_ok(int64_t m, int64_t n, int64_t k) {
-  return m > 0 && n > 0 && k > 0 && m % kGemmBM == 0 && n % kGemmBN == 0 &&
-         k % kGemmBK == 0 && m <= (1 << 24) && n <= (1 << 24) &&
-         k <= (1 << 24) && (m / kGemmBM) * (n / kGemmBN) <= (1 << 22);
+  return gemm_grid_ok(m, n) && k > 0 && k % kGemmBK == 0 && k <= (1 << 24);
+}
+
+// Flat grid of `block` x `block` output tiles over [m, n], row-major.
+struct GemmGrid { int tiles_n, tiles; };
+inline GemmGrid gemm_grid(int64_t m, int64_t n, int block) {
+  const int tiles_n = (int)(n / block);
+  return {tiles_n, (int)(m / block) * tiles_n};
 }
 
 // `buf` is a stored [rows, cols] bf16 matrix, cols % 8 == 0.
@@ -301,24 +355,22 @@ inline void launch_gemm_fill(hipStream_t stream, void* buf, int which,
 inline void launch_gemm_bf16_nt(hipStream_t stream, const void* a,
                                 const void* bt, void* c, void* where,
                                 int64_t m, int64_t n, int64_t k) {
-  const int tiles_n = (int)(n / kGemmBN);
-  const int tiles = (int)(m / kGemmBM) * tiles_n;
-  hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3(tiles), dim3(256), 0, stream,
+  const GemmGrid g = gemm_grid(m, n, kGemmBM);
+  hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3(g.tiles), dim3(256), 0, stream,
                      static_cast<const uint16_t*>(a),
                      static_cast<const uint16_t*>(bt), static_cast<float*>(c),
-                     static_cast<int*>(where), (int)k, (int)n, tiles_n);
+                     static_cast<int*>(where), (int)k, (int)n, g.tiles_n);
 }
 
 // Caller guarantees gemm_shape_ok(m, n, k) and k <= kGemmExactMaxK.
 inline void launch_gemm_ref_int(hipStream_t stream, const void* a,
                                 const void* bt, void* gold, int64_t m,
                                 int64_t n, int64_t k) {
-  const int tiles_n = (int)(n / kGemmRefTile);
-  const int tiles = (int)(m / kGemmRefTile) * tiles_n;
-  hipLaunchKernelGGL(gemm_ref_int_kernel, dim3(tiles), dim3(256), 0, stream,
+  const GemmGrid g = gemm_grid(m, n, kGemmRefTile);
+  hipLaunchKernelGGL(gemm_ref_int_kernel, dim3(g.tiles), dim3(256), 0, stream,
                      static_cast<const uint16_t*>(a),
                      static_cast<const uint16_t*>(bt),
-                     static_cast<float*>(gold), (int)k, (int)n, tiles_n);
+                     static_cast<float*>(gold), (int)k, (int)n, g.tiles_n);
 }
 
 inline void launch_buf_compare(hipStream_t stream, const void* buf,

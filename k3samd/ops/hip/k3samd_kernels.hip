@@ -381,12 +381,9 @@ torch::Tensor mfma_gemm16(torch::Tensor A, torch::Tensor B, int64_t layout) {
                B.size(1) == 16,
            "A must be [16,32], B [32,16]");
   auto D = torch::empty({16, 16}, A.options().dtype(torch::kFloat32));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(k3samd_kern::mfma_gemm16_kernel, dim3(1), dim3(64), 0,
-                     stream,
-                     reinterpret_cast<const uint16_t*>(A.data_ptr()),
-                     reinterpret_cast<const uint16_t*>(B.data_ptr()),
-                     D.data_ptr<float>(), (int)layout);
+  k3samd_kern::launch_mfma_gemm16(at::hip::getCurrentHIPStream(),
+                                  A.data_ptr(), B.data_ptr(),
+                                  D.data_ptr<float>(), (int)layout);
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return D;
 }
@@ -408,13 +405,9 @@ torch::Tensor mx_gemm16(torch::Tensor A, torch::Tensor B, int64_t fmt) {
                B.size(1) == kb,
            "A must be [16,KB], B [16,KB] (B column-major-packed)");
   auto D = torch::empty({16, 16}, A.options().dtype(torch::kFloat32));
-  auto stream = at::hip::getCurrentHIPStream();
-  auto kernel = fmt == 0 ? k3samd_kern::mx_gemm16_kernel<0>
-                         : k3samd_kern::mx_gemm16_kernel<4>;
-  hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, stream,
-                     reinterpret_cast<const uint8_t*>(A.data_ptr()),
-                     reinterpret_cast<const uint8_t*>(B.data_ptr()),
-                     D.data_ptr<float>());
+  k3samd_kern::launch_mx_gemm16(at::hip::getCurrentHIPStream(), (int)fmt,
+                                A.data_ptr(), B.data_ptr(),
+                                D.data_ptr<float>());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return D;
 }

@@ -30,13 +30,10 @@
 //
 // mx_gemm_nt_kernel, shape contract M % 128 == N % 128 == 0, K % 128 == 0
 // (fp8) or K % 256 == 0 (fp4), checked on the host; no edge handling.
-// One K-step is 128 BYTES of every row in both formats, so the geometry is
-// that of gemm_bf16_nt_kernel: 128x128 block, 256 threads = 2x2 waves of
-// 64x64 (acc[4][4] of f32x4), operand tiles of 128 rows x 128 bytes staged
-// by global_load_lds width 16, chunk c of row r kept at slot
-// c ^ ((r >> 1) & 7) (XOR on the staging source address and on the
-// fragment read), two __syncthreads() per step, where[tile] = {XCC_ID,
-// HW_ID}. What differs is the fragment: an fp8 lane reads the two chunks
+// One K-step is kGemmStepBytes = 128 BYTES of every row in both formats,
+// so tile, staging, swizzle, barriers, placement record and epilogue are
+// gemm_kernels.h's GemmTile and gemm_* helpers, described at the top of
+// that file. What differs is the fragment: an fp8 lane reads the two chunks
 // q and 4 + q (q = lane >> 4) for one MFMA per step; an fp4 lane reads
 // chunk s*4 + q into the low four dwords for MFMA s = 0, 1 of the step.
 // Scale bytes come straight from global memory, one zero-extended byte
@@ -57,16 +54,13 @@
 
 namespace k3samd_kern {
 
-constexpr int kMxStepBytes = 128;  // row bytes per K-step, both formats
-constexpr int kMxTileBytes = kGemmBM * kMxStepBytes;  // 16 KiB per operand
-
 #if K3_HAS_MFMA
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 #endif
 
 // K elements per K-step of mx_gemm_nt_kernel.
 K3_GEMM_HD inline int mx_step_k(int fmt) {
-  return fmt == kMxFmtFp4 ? 2 * kMxStepBytes : kMxStepBytes;
+  return fmt == kMxFmtFp4 ? 2 * kGemmStepBytes : kGemmStepBytes;
 }
 
 // D[16,16] = (A o SA)[16,128] . (B o SB)[128,16]. A and B are packed as for
@@ -157,62 +151,32 @@ __global__ __launch_bounds__(256, 2) void mx_gemm_nt_kernel(
     float* __restrict__ C, int* __restrict__ where, int KB, int N,
     int tiles_n) {
 #if K3_HAS_MFMA
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kMxTileBytes];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kGemmTileBytes];
   unsigned char* const lds_a = lds;
-  unsigned char* const lds_b = lds + kMxTileBytes;
+  unsigned char* const lds_b = lds + kGemmTileBytes;
   constexpr int kSub = FMT == 0 ? 1 : 2;  // MFMAs along k per K-step
 
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int tile = blockIdx.x;
-  const int64_t brow = (int64_t)(tile / tiles_n) * kGemmBM;
-  const int64_t bcol = (int64_t)(tile % tiles_n) * kGemmBN;
+  const GemmTile t = gemm_tile(tiles_n);
+  if (where != nullptr && threadIdx.x == 0) cu_record_placement(where, t.tile);
 
-  if (where != nullptr && tid == 0) {
-    where[2 * tile] = (int)__builtin_amdgcn_s_getreg(kHwRegXccId);
-    where[2 * tile + 1] = (int)__builtin_amdgcn_s_getreg(kHwRegHwId);
-  }
-
-  // Staging, as in gemm_bf16_nt_kernel: instruction i of wave `wid` fills
-  // tile rows (i*4 + wid)*8 .. +7; lane l lands on row +(l>>3), chunk slot
-  // l&7, and fetches source chunk slot ^ ((row >> 1) & 7).
-  const int srow = wid * 8 + (lane >> 3);
-  const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
-  const uint8_t* a_src = A + (brow + srow) * (int64_t)KB + schunk * 16;
-  const uint8_t* b_src = Bt + (bcol + srow) * (int64_t)KB + schunk * 16;
+  const unsigned char* a_src = gemm_stage_src(A, t.brow, KB, t);
+  const unsigned char* b_src = gemm_stage_src(Bt, t.bcol, KB, t);
   const int64_t step32 = 32 * (int64_t)KB;  // 32 rows further down
-
-  const int wr = wid >> 1, wc = wid & 1;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int fsw = (fr >> 1) & 7;
-  const unsigned char* a_rd = lds_a + (wr * 64 + fr) * 128;
-  const unsigned char* b_rd = lds_b + (wc * 64 + fr) * 128;
+  const unsigned char* a_rd = lds_a + (t.wr * 64 + t.fr) * kGemmStepBytes;
+  const unsigned char* b_rd = lds_b + (t.wc * 64 + t.fr) * kGemmStepBytes;
 
   // Scales: this lane's fragment m (n) is row brow + wr*64 + m*16 + fr,
   // and in MFMA s of a step it holds k-block step * 4 * kSub + s * 4 + fq.
   const int SK = KB / (kMxScaleBlock / (FMT == 0 ? 1 : 2));  // K / 32
-  const uint8_t* sa_src = SA + (brow + wr * 64 + fr) * (int64_t)SK + fq;
-  const uint8_t* sb_src = SB + (bcol + wc * 64 + fr) * (int64_t)SK + fq;
+  const uint8_t* sa_src = SA + (t.brow + t.wr * 64 + t.fr) * (int64_t)SK + t.fq;
+  const uint8_t* sb_src = SB + (t.bcol + t.wc * 64 + t.fr) * (int64_t)SK + t.fq;
   const int64_t sstep16 = 16 * (int64_t)SK;  // 16 rows further down
+  f32x4 acc[4][4] = {};
 
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  for (int kb0 = 0; kb0 < KB; kb0 += kMxStepBytes) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int dst = (i * 4 + wid) * 1024;  // wave-uniform
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(a_src + i * step32 + kb0),
-          (__attribute__((address_space(3))) void*)(lds_a + dst), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(b_src + i * step32 + kb0),
-          (__attribute__((address_space(3))) void*)(lds_b + dst), 16, 0, 0);
-    }
+  for (int kb0 = 0; kb0 < KB; kb0 += kGemmStepBytes) {
+    gemm_stage(a_src + kb0, b_src + kb0, step32, lds_a, lds_b, t.wid);
     // byte 0 = the scale, bytes 1..3 zero; opsel 0 selects byte 0
-    const int sblk = kb0 / kMxStepBytes * 4 * kSub;
+    const int sblk = kb0 / kGemmStepBytes * 4 * kSub;
     int sa[kSub][4], sb[kSub][4];
 #pragma unroll
     for (int s = 0; s < kSub; ++s)
@@ -227,33 +191,33 @@ __global__ __launch_bounds__(256, 2) void mx_gemm_nt_kernel(
       i32x8 af[4], bfr[4];
       const i32x4 zero = {0, 0, 0, 0};
       if constexpr (FMT == 0) {
-        const int c0 = (fq ^ fsw) << 4, c1 = ((4 + fq) ^ fsw) << 4;
+        const int c0 = (t.fq ^ t.fsw) << 4, c1 = ((4 + t.fq) ^ t.fsw) << 4;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-          const unsigned char* p = a_rd + m * 16 * 128;
+          const unsigned char* p = a_rd + m * kGemmFragBytes;
           af[m] = __builtin_shufflevector(
               *reinterpret_cast<const i32x4*>(p + c0),
               *reinterpret_cast<const i32x4*>(p + c1), 0, 1, 2, 3, 4, 5, 6, 7);
         }
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-          const unsigned char* p = b_rd + n * 16 * 128;
+          const unsigned char* p = b_rd + n * kGemmFragBytes;
           bfr[n] = __builtin_shufflevector(
               *reinterpret_cast<const i32x4*>(p + c0),
               *reinterpret_cast<const i32x4*>(p + c1), 0, 1, 2, 3, 4, 5, 6, 7);
         }
       } else {
-        const int coff = ((s * 4 + fq) ^ fsw) << 4;
+        const int coff = ((s * 4 + t.fq) ^ t.fsw) << 4;
 #pragma unroll
         for (int m = 0; m < 4; ++m)
           af[m] = __builtin_shufflevector(
-              *reinterpret_cast<const i32x4*>(a_rd + m * 16 * 128 + coff), zero,
-              0, 1, 2, 3, 4, 5, 6, 7);
+              *reinterpret_cast<const i32x4*>(a_rd + m * kGemmFragBytes + coff),
+              zero, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
         for (int n = 0; n < 4; ++n)
           bfr[n] = __builtin_shufflevector(
-              *reinterpret_cast<const i32x4*>(b_rd + n * 16 * 128 + coff), zero,
-              0, 1, 2, 3, 4, 5, 6, 7);
+              *reinterpret_cast<const i32x4*>(b_rd + n * kGemmFragBytes + coff),
+              zero, 0, 1, 2, 3, 4, 5, 6, 7);
       }
 #pragma unroll
       for (int m = 0; m < 4; ++m)
@@ -268,15 +232,7 @@ __global__ __launch_bounds__(256, 2) void mx_gemm_nt_kernel(
     }
     __syncthreads();  // everyone is done reading before the next stage
   }
-
-  float* c_wave = C + (brow + wr * 64 + fq * 4) * (int64_t)N + bcol + wc * 64 + fr;
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        c_wave[(m * 16 + j) * (int64_t)N + n * 16] = acc[m][n][j];
+  gemm_store_acc(C, N, t, acc);
 #else
   (void)A; (void)SA; (void)Bt; (void)SB; (void)C; (void)where; (void)KB;
   (void)N; (void)tiles_n;
@@ -319,12 +275,7 @@ __global__ __launch_bounds__(256) void mx_gemm_ref_int_kernel(
   const int SK = K / kMxScaleBlock;
   const int row = tid >> 2, c = tid & 3;  // this thread's 16 k: c*16 .. +15
 
-  int acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0;
-
+  int acc[4][4] = {};
   for (int k0 = 0; k0 < K; k0 += 64) {
     const int k = k0 + c * 16;
     const int sha = (int)SA[(brow + row) * (int64_t)SK + k / kMxScaleBlock] - 127;
@@ -353,37 +304,18 @@ __global__ __launch_bounds__(256) void mx_gemm_ref_int_kernel(
     }
     __syncthreads();
 #pragma unroll
-    for (int kw = 0; kw < 16; ++kw) {
-      int a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = as[ty * 4 + i][kw];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = bs[tx * 4 + j][kw];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = gemm_dot4_i8(a[i], b[j], acc[i][j]);
-    }
+    for (int kw = 0; kw < 16; ++kw) gemm_ref_dot_word(as, bs, tx, ty, kw, acc);
     __syncthreads();
   }
-  const float unit = FMT == 0 ? 1.0f : 0.25f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f4 v = {(float)acc[i][0] * unit, (float)acc[i][1] * unit,
-            (float)acc[i][2] * unit, (float)acc[i][3] * unit};
-    *reinterpret_cast<f4*>(gold + (brow + ty * 4 + i) * (int64_t)N + bcol +
-                           tx * 4) = v;
-  }
+  gemm_ref_store<FMT == 0 ? 1 : 4>(gold, N, brow, bcol, tx, ty, acc);
 }
 
 // ---- host-side launchers (no sync, errors via hipGetLastError) ----
 
 // True when (fmt, m, n, k) meets mx_gemm_nt_kernel's shape contract.
 inline bool mx_shape_ok(int fmt, int64_t m, int64_t n, int64_t k) {
-  return mx_fmt_ok(fmt) && m > 0 && n > 0 && k > 0 && m % kGemmBM == 0 &&
-         n % kGemmBN == 0 && k % mx_step_k(fmt) == 0 && m <= (1 << 24) &&
-         n <= (1 << 24) && k <= (1 << 24) &&
-         (m / kGemmBM) * (n / kGemmBN) <= (1 << 22);
+  return mx_fmt_ok(fmt) && gemm_grid_ok(m, n) && k > 0 &&
+         k % mx_step_k(fmt) == 0 && k <= (1 << 24);
 }
 
 // `elems` is a stored [rows][k] element matrix (mx_row_bytes(fmt, k) bytes
@@ -419,16 +351,15 @@ inline void launch_mx_gemm_nt(hipStream_t stream, int fmt, const void* a,
                               const void* sa, const void* bt, const void* sb,
                               void* c, void* where, int64_t m, int64_t n,
                               int64_t k) {
-  const int tiles_n = (int)(n / kGemmBN);
-  const int tiles = (int)(m / kGemmBM) * tiles_n;
+  const GemmGrid g = gemm_grid(m, n, kGemmBM);
   auto kernel = fmt == kMxFmtFp8 ? mx_gemm_nt_kernel<0> : mx_gemm_nt_kernel<4>;
-  hipLaunchKernelGGL(kernel, dim3(tiles), dim3(256), 0, stream,
+  hipLaunchKernelGGL(kernel, dim3(g.tiles), dim3(256), 0, stream,
                      static_cast<const uint8_t*>(a),
                      static_cast<const uint8_t*>(sa),
                      static_cast<const uint8_t*>(bt),
                      static_cast<const uint8_t*>(sb), static_cast<float*>(c),
                      static_cast<int*>(where), (int)mx_row_bytes(fmt, k),
-                     (int)n, tiles_n);
+                     (int)n, g.tiles_n);
 }
 
 // Caller guarantees mx_shape_ok(fmt, m, n, k) and k <= kMxExactMaxK.
@@ -436,16 +367,15 @@ inline void launch_mx_gemm_ref_int(hipStream_t stream, int fmt, const void* a,
                                    const void* sa, const void* bt,
                                    const void* sb, void* gold, int64_t m,
                                    int64_t n, int64_t k) {
-  const int tiles_n = (int)(n / kGemmRefTile);
-  const int tiles = (int)(m / kGemmRefTile) * tiles_n;
+  const GemmGrid g = gemm_grid(m, n, kGemmRefTile);
   auto kernel = fmt == kMxFmtFp8 ? mx_gemm_ref_int_kernel<0>
                                  : mx_gemm_ref_int_kernel<4>;
-  hipLaunchKernelGGL(kernel, dim3(tiles), dim3(256), 0, stream,
+  hipLaunchKernelGGL(kernel, dim3(g.tiles), dim3(256), 0, stream,
                      static_cast<const uint8_t*>(a),
                      static_cast<const uint8_t*>(sa),
                      static_cast<const uint8_t*>(bt),
                      static_cast<const uint8_t*>(sb),
-                     static_cast<float*>(gold), (int)k, (int)n, tiles_n);
+                     static_cast<float*>(gold), (int)k, (int)n, g.tiles_n);
 }
 
 }  // namespace k3samd_kern

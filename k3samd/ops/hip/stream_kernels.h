@@ -1,8 +1,9 @@
 // CDNA4 (gfx950) device kernels and their host-side launch_* helpers,
 // shared by the torch extension (k3samd_kernels.hip) and the standalone
 // in-pod smoke binary (native/hipsmoke/mi_stream.hip); both launch the
-// STREAM and MFMA-throughput kernels only through the helpers at the end
-// of this file. Pure HIP — no torch dependency.
+// STREAM, MFMA-throughput and single-tile MFMA kernels only through the
+// helpers at the end of this file (mi-stream --tune alone launches its
+// stream_triad_gs_kernel sweep itself). Pure HIP — no torch dependency.
 //
 // Design (MI355X-first):
 //  * 16 B/lane (float4 ext-vector) loads/stores — 1 KiB per wave64 vector
@@ -263,11 +264,16 @@ static __global__ void mfma_throughput_mx_kernel(float* __restrict__ out,
 #endif
 }
 
+// C/D map of every 16x16 MFMA: register r of lane l, in row-major D[16][16].
+__device__ __forceinline__ int mfma_tile16_index(int l, int r) {
+  return ((l >> 4) * 4 + r) * 16 + (l & 15);
+}
+
 // Single-tile D[16x16] = A[16x32] * B[32x16] through one
 // v_mfma_f32_16x16x32_bf16 for numerics validation.
 //   layout 0 (validated on MI355X): lane l holds A[l&15][(l>>4)*8 + j]
 //   layout 1 (rejected candidate) : A[l&15][(l>>4)*4 + (j&3) + 16*(j>>2)]
-// B mirrors A with row/col swapped; C/D: col=lane&15, row=(lane>>4)*4+reg.
+// B mirrors A with row/col swapped; C/D: mfma_tile16_index.
 static __global__ void mfma_gemm16_kernel(const uint16_t* __restrict__ A,
                                           const uint16_t* __restrict__ B,
                                           float* __restrict__ D, int layout) {
@@ -284,9 +290,7 @@ static __global__ void mfma_gemm16_kernel(const uint16_t* __restrict__ A,
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc, 0, 0, 0);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    D[((l >> 4) * 4 + r) * 16 + (l & 15)] = acc[r];
-  }
+  for (int r = 0; r < 4; ++r) D[mfma_tile16_index(l, r)] = acc[r];
 #else
   (void)A; (void)B; (void)D; (void)layout;
 #endif
@@ -303,7 +307,7 @@ static __global__ void mfma_gemm16_kernel(const uint16_t* __restrict__ A,
 //   lane l holds A[l&15][(l>>4)*32 + j]  for j = 0..31 (fp8: byte j of
 //   the 32-byte operand; fp4: nibble j of the 16-byte operand, low
 //   nibble first), B mirrored with row/col swapped.
-// C/D use the shape-determined map col=lane&15, row=(lane>>4)*4+reg
+// C/D use the shape-determined map of mfma_tile16_index
 // (dtype-independent per the CDNA4 ISA).
 //
 // A is packed row-major (fp8: 1 B/elem, stride 128; fp4: 2 elems/B, low
@@ -345,8 +349,7 @@ static __global__ void mx_gemm16_kernel(const uint8_t* __restrict__ A,
   // operand class are not documented — don't rely on it.
   __asm__ volatile("" ::"v"(scale));
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    D[((l >> 4) * 4 + r) * 16 + (l & 15)] = acc[r];
+  for (int r = 0; r < 4; ++r) D[mfma_tile16_index(l, r)] = acc[r];
 #else
   (void)A; (void)B; (void)D;
 #endif
@@ -464,6 +467,21 @@ inline void launch_mfma_throughput(hipStream_t stream, MfmaKind kind,
                                              : mfma_throughput_mx_kernel<4>;
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kThreadsPerBlock), 0, stream,
                      out, iters);
+}
+
+// Single-tile numerics kernels, one wave; the caller checks fmt is 0 or 4.
+inline void launch_mfma_gemm16(hipStream_t stream, const void* A,
+                               const void* B, float* D, int layout) {
+  hipLaunchKernelGGL(mfma_gemm16_kernel, dim3(1), dim3(64), 0, stream,
+                     static_cast<const uint16_t*>(A),
+                     static_cast<const uint16_t*>(B), D, layout);
+}
+inline void launch_mx_gemm16(hipStream_t stream, int fmt, const void* A,
+                             const void* B, float* D) {
+  auto kernel = fmt == 0 ? mx_gemm16_kernel<0> : mx_gemm16_kernel<4>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, stream,
+                     static_cast<const uint8_t*>(A),
+                     static_cast<const uint8_t*>(B), D);
 }
 
 }  // namespace k3samd_kern

@@ -112,8 +112,7 @@ bool self_check() {
     }
     (void)hipMemcpy(A, hA.data(), hA.size() * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(B, hB.data(), hB.size() * 2, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(mfma_gemm16_kernel, dim3(1), dim3(64), 0, 0,
-                       (const uint16_t*)A, (const uint16_t*)B, (float*)D, 0);
+    launch_mfma_gemm16(0, A, B, D, 0);
     std::vector<float> hD(256);
     (void)hipMemcpy(hD.data(), D, 256 * 4, hipMemcpyDeviceToHost);
     for (int i = 0; i < 16; ++i)
@@ -152,8 +151,7 @@ bool self_check() {
       }
     (void)hipMemcpy(A, hA.data(), hA.size(), hipMemcpyHostToDevice);
     (void)hipMemcpy(B, hB.data(), hB.size(), hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(mx_gemm16_kernel<0>, dim3(1), dim3(64), 0, 0,
-                       (const uint8_t*)A, (const uint8_t*)B, (float*)D);
+    launch_mx_gemm16(0, 0, A, B, D);
     std::vector<float> hD(256);
     (void)hipMemcpy(hD.data(), D, 256 * 4, hipMemcpyDeviceToHost);
     for (int i = 0; i < 16; ++i)
