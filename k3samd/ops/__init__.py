@@ -159,9 +159,10 @@ GEMM_EXACT_MAX_K = 32768  # 256 * K <= 2^23: every partial sum exact in fp32
 
 
 def gemm_fill(buf, which, seed, rows, cols):
-    """Write generator operands as bf16 into the stored [rows, cols] matrix
-    `buf`: which = 0 is A[M,K]; which = 1 is Bt[N,K], whose element [n][k]
-    is gemm_operand(seed, 1, row=k, col=n)."""
+    """Write generator operands into the stored [rows, cols] matrix `buf`
+    in its own dtype (bfloat16, float16, int8, float32 or float64; cols a
+    whole number of 16-byte cells): which = 0 is A[M,K]; which = 1 is
+    Bt[N,K], whose element [n][k] is gemm_operand(seed, 1, row=k, col=n)."""
     _require_native().gemm_fill(buf, int(which), int(seed) & _U64, int(rows),
                                 int(cols))
 
@@ -179,9 +180,48 @@ def gemm_ref_int(A, Bt, out=None):
     return _require_native().gemm_ref_int(A, Bt, out)
 
 
+# ---- verified fp16 / int8 / fp32 / fp64 GEMM (hip/gemm_dense_kernels.h) ----
+
+
+def _gemm_formats():
+    try:
+        import torch
+    except ImportError:
+        return {}
+    return {"bf16": (torch.bfloat16, torch.float32, 64),
+            "fp16": (torch.float16, torch.float32, 64),
+            "int8": (torch.int8, torch.int32, 128),
+            "fp32": (torch.float32, torch.float32, 32),
+            "fp64": (torch.float64, torch.float64, 16)}
+
+
+# name -> (operand dtype, result dtype, K-step in elements): one K-step is
+# 128 bytes of every operand row. bf16 is gemm_bf16_nt / gemm_ref_int; the
+# other four are gemm_dense_nt / gemm_dense_ref_int.
+GEMM_FORMATS = _gemm_formats()
+
+
+def gemm_dense_nt(A, Bt, out=None, where=None):
+    """C[M,N] = A[M,K] @ Bt[N,K].T on the matrix pipe of A's dtype, for any
+    data: float16 (v_mfma_f32_16x16x32_f16, C float32), int8
+    (v_mfma_i32_16x16x64_i8, C int32), float32 (v_mfma_f32_16x16x4_f32, C
+    float32) or float64 (v_mfma_f64_16x16x4_f64, C float64). M % 128 ==
+    N % 128 == 0, K a whole number of the format's K-steps (GEMM_FORMATS).
+    `where` as for gemm_bf16_nt."""
+    return _require_native().gemm_dense_nt(A, Bt, out, where)
+
+
+def gemm_dense_ref_int(A, Bt, out=None):
+    """The same product by int32 VALU arithmetic (no MFMA), in the format's
+    result dtype. For operands holding integers in [-128, 127], K <= 32768;
+    a float32 result is exact only while |sum| <= 2^24."""
+    return _require_native().gemm_dense_ref_int(A, Bt, out)
+
+
 def buf_compare(buf, expected, report):
     """Bitwise compare of two equally sized GPU buffers, accumulated into
-    a mem_report_new() report; dword indices count 32-bit elements."""
+    a mem_report_new() report; dword indices count 32-bit elements (two
+    per float64 element, low half first)."""
     _require_native().buf_compare(buf, expected, report)
 
 

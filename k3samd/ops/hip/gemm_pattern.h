@@ -20,6 +20,14 @@
 // fp32 holds exactly. The correct C is therefore unique whatever order the
 // matrix pipe accumulates in, and can be compared bitwise. K <= 32768
 // (kGemmExactMaxK) is a hard argument check on the exact path.
+//
+// The other dense formats (gemm_dense_kernels.h) take the same operands,
+// and the same cap. fp16 and fp32 inherit the argument as it stands: the
+// operands have at most 5 significant bits, which fp16 (11) and fp32 (24)
+// hold without rounding, and accumulation is fp32, so |sum| <= 256*K <=
+// 2^23 is exact under any association. int8 accumulates in int32 and fp64
+// in fp64: exact while |sum| < 2^31 and <= 2^53, far beyond the cap.
+// Every format is therefore compared bitwise.
 
 #pragma once
 

@@ -9,6 +9,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "cu_test_kernels.h"
+#include "gemm_dense_kernels.h"
 #include "gemm_kernels.h"
 #include "hostlink_kernels.h"
 #include "memtest_kernels.h"
@@ -19,7 +20,7 @@ namespace {
 
 using k3samd_kern::f4;
 
-#define K3_CHECK(cond, msg) TORCH_CHECK(cond, "k3samd: ", msg)
+#define K3_CHECK(cond, ...) TORCH_CHECK(cond, "k3samd: ", __VA_ARGS__)
 
 void check_stream_args(const torch::Tensor& t) {
   K3_CHECK(t.is_cuda(), "tensor must be on GPU");
@@ -96,13 +97,17 @@ GemmDims check_gemm_operands(const torch::Tensor& A, const torch::Tensor& Bt) {
   return d;
 }
 
-// fp32 [M,N] result buffer: the caller's `out` after checks, or a new one.
+// [M,N] result buffer (fp32 unless a dense format says otherwise): the
+// caller's `out` after checks, or a new one.
 torch::Tensor gemm_result(const c10::optional<torch::Tensor>& out,
-                          const torch::Tensor& A, const GemmDims& d) {
-  if (!out.has_value())
-    return torch::empty({d.m, d.n}, A.options().dtype(torch::kFloat32));
+                          const torch::Tensor& A, const GemmDims& d,
+                          torch::ScalarType type = torch::kFloat32) {
+  if (!out.has_value()) return torch::empty({d.m, d.n}, A.options().dtype(type));
   const torch::Tensor& o = *out;
-  K3_CHECK(o.scalar_type() == torch::kFloat32, "out must be float32");
+  K3_CHECK(o.scalar_type() == type, "out must be ",
+           type == torch::kInt32     ? "int32"
+           : type == torch::kFloat64 ? "float64"
+                                     : "float32");
   K3_CHECK(o.dim() == 2 && o.size(0) == d.m && o.size(1) == d.n,
            "out must be [M,N]");
   K3_CHECK(o.is_contiguous(), "out must be contiguous");
@@ -127,6 +132,46 @@ void* check_tile_where(const c10::optional<torch::Tensor>& where,
   K3_CHECK(w.is_cuda() && w.device() == A.device(),
            "where must be on the same GPU as A");
   return w.data_ptr();
+}
+
+// The dense format (gemm_dense_kernels.h) of an operand dtype, 0 for none.
+int gemm_dense_fmt_of(const torch::Tensor& t) {
+  switch (t.scalar_type()) {
+    case torch::kFloat16: return k3samd_kern::kGemmFmtFp16;
+    case torch::kInt8: return k3samd_kern::kGemmFmtInt8;
+    case torch::kFloat32: return k3samd_kern::kGemmFmtFp32;
+    case torch::kFloat64: return k3samd_kern::kGemmFmtFp64;
+    default: return 0;
+  }
+}
+
+torch::ScalarType gemm_dense_result_type(int fmt) {
+  return fmt == k3samd_kern::kGemmFmtInt8   ? torch::kInt32
+         : fmt == k3samd_kern::kGemmFmtFp64 ? torch::kFloat64
+                                            : torch::kFloat32;
+}
+
+// check_gemm_operands for the dense formats, in the same order; the format
+// comes from A's dtype.
+GemmDims check_gemm_dense_operands(const torch::Tensor& A,
+                                   const torch::Tensor& Bt, int* fmt) {
+  *fmt = gemm_dense_fmt_of(A);
+  K3_CHECK(*fmt != 0 && Bt.scalar_type() == A.scalar_type(),
+           "A and Bt must both be float16, int8, float32 or float64");
+  K3_CHECK(A.dim() == 2 && Bt.dim() == 2, "A must be [M,K] and Bt [N,K]");
+  K3_CHECK(A.is_contiguous() && Bt.is_contiguous(),
+           "A and Bt must be contiguous");
+  K3_CHECK(A.size(1) == Bt.size(1), "A [M,K] and Bt [N,K] disagree on K");
+  GemmDims d{A.size(0), Bt.size(0), A.size(1)};
+  K3_CHECK(k3samd_kern::gemm_dense_shape_ok(*fmt, d.m, d.n, d.k),
+           "gemm shape contract: M % 128 == 0, N % 128 == 0, K % ",
+           k3samd_kern::gemm_dense_step_k(*fmt), " == 0 (",
+           k3samd_kern::gemm_dense_fmt_name(*fmt), "), all > 0");
+  K3_CHECK(aligned16(A) && aligned16(Bt),
+           "A and Bt data pointers must be 16-byte aligned");
+  K3_CHECK(A.is_cuda() && Bt.is_cuda(), "A and Bt must be on GPU");
+  K3_CHECK(A.device() == Bt.device(), "A and Bt must be on the same GPU");
+  return d;
 }
 
 bool is_u8_matrix(const torch::Tensor& t) {
@@ -459,14 +504,22 @@ void mem_verify_fill(torch::Tensor buf, torch::Tensor report,
 void gemm_fill(torch::Tensor buf, int64_t which, uint64_t seed, int64_t rows,
                int64_t cols) {
   K3_CHECK(which == 0 || which == 1, "which must be 0 (A) or 1 (Bt)");
-  K3_CHECK(buf.scalar_type() == torch::kBFloat16, "buffer must be bfloat16");
-  K3_CHECK(rows > 0 && cols > 0 && cols % 8 == 0 && rows <= (1 << 24) &&
+  const int fmt = gemm_dense_fmt_of(buf);  // 0: the bf16 path
+  K3_CHECK(fmt != 0 || buf.scalar_type() == torch::kBFloat16,
+           "buffer must be bfloat16");
+  const int per_cell = fmt ? 16 / k3samd_kern::gemm_dense_elem_bytes(fmt) : 8;
+  K3_CHECK(rows > 0 && cols > 0 && cols % per_cell == 0 && rows <= (1 << 24) &&
                cols <= (1 << 24),
-           "rows and cols must be > 0 and cols a multiple of 8");
+           "rows and cols must be > 0 and cols a multiple of ", per_cell);
   K3_CHECK(buf.numel() == rows * cols, "buffer must hold rows * cols elements");
   check_mem_buf(buf);
-  k3samd_kern::launch_gemm_fill(at::hip::getCurrentHIPStream(), buf.data_ptr(),
-                                (int)which, seed, rows, cols);
+  if (fmt)
+    k3samd_kern::launch_gemm_dense_fill(at::hip::getCurrentHIPStream(), fmt,
+                                        buf.data_ptr(), (int)which, seed, rows,
+                                        cols);
+  else
+    k3samd_kern::launch_gemm_fill(at::hip::getCurrentHIPStream(),
+                                  buf.data_ptr(), (int)which, seed, rows, cols);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -498,6 +551,43 @@ torch::Tensor gemm_ref_int(torch::Tensor A, torch::Tensor Bt,
   k3samd_kern::launch_gemm_ref_int(at::hip::getCurrentHIPStream(),
                                    A.data_ptr(), Bt.data_ptr(),
                                    gold.data_ptr(), d.m, d.n, d.k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return gold;
+}
+
+// ---- verified fp16 / int8 / fp32 / fp64 GEMM (gemm_dense_kernels.h) ----
+// The format follows A's dtype; C is float32, int32, float32 or float64.
+
+// C[M,N] = A[M,K] . Bt[N,K]^T on the format's matrix pipe; any data.
+// `where` as for gemm_bf16_nt.
+torch::Tensor gemm_dense_nt(torch::Tensor A, torch::Tensor Bt,
+                            c10::optional<torch::Tensor> out,
+                            c10::optional<torch::Tensor> where) {
+  int fmt;
+  GemmDims d = check_gemm_dense_operands(A, Bt, &fmt);
+  void* where_ptr = check_tile_where(where, d, A);
+  torch::Tensor C = gemm_result(out, A, d, gemm_dense_result_type(fmt));
+  k3samd_kern::launch_gemm_dense_nt(at::hip::getCurrentHIPStream(), fmt,
+                                    A.data_ptr(), Bt.data_ptr(), C.data_ptr(),
+                                    where_ptr, d.m, d.n, d.k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return C;
+}
+
+// The same product in int32 VALU arithmetic (no MFMA). Operands must hold
+// integers in [-128, 127]; K <= 32768 keeps every sum within int32, and
+// every sum of generator operands exactly representable in fp32.
+torch::Tensor gemm_dense_ref_int(torch::Tensor A, torch::Tensor Bt,
+                                 c10::optional<torch::Tensor> out) {
+  K3_CHECK(A.dim() != 2 || A.size(1) <= k3samd_kern::kGemmExactMaxK,
+           "gemm_dense_ref_int needs K <= 32768 (exactness bound 256*K <= "
+           "2^23)");
+  int fmt;
+  GemmDims d = check_gemm_dense_operands(A, Bt, &fmt);
+  torch::Tensor gold = gemm_result(out, A, d, gemm_dense_result_type(fmt));
+  k3samd_kern::launch_gemm_dense_ref_int(at::hip::getCurrentHIPStream(), fmt,
+                                         A.data_ptr(), Bt.data_ptr(),
+                                         gold.data_ptr(), d.m, d.n, d.k);
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return gold;
 }
@@ -860,6 +950,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_bf16_nt", &gemm_bf16_nt, py::arg("A"), py::arg("Bt"),
         py::arg("out") = py::none(), py::arg("where") = py::none());
   m.def("gemm_ref_int", &gemm_ref_int, py::arg("A"), py::arg("Bt"),
+        py::arg("out") = py::none());
+  m.def("gemm_dense_nt", &gemm_dense_nt, py::arg("A"), py::arg("Bt"),
+        py::arg("out") = py::none(), py::arg("where") = py::none());
+  m.def("gemm_dense_ref_int", &gemm_dense_ref_int, py::arg("A"), py::arg("Bt"),
         py::arg("out") = py::none());
   m.def("buf_compare", &buf_compare, py::arg("buf"), py::arg("expected"),
         py::arg("report"));

@@ -7,6 +7,14 @@
 // The driver is a template over a *problem* type that supplies only what
 // differs between the operand formats:
 //
+//   using Result;                        element of C and of the gold: float,
+//                                        int32_t or double
+//   static constexpr int kPoison;        the byte C is preset with, so that
+//                                        an element the kernel skipped cannot
+//                                        equal the gold: 0xFF (NaN) for float
+//                                        and double; 0x80 for int32, where -1
+//                                        is a legitimate product and
+//                                        0x80808080 lies outside +-2^23
 //   static constexpr const char* kTag;   "gemmtest" / "mxgemmtest"
 //   static constexpr int64_t kSelftestK; K of the 256 x 256 self-test product
 //   P fresh() const;                     an unallocated problem of the same
@@ -15,9 +23,9 @@
 //   void fill(seed);                     the launch_* calls, on the null
 //   void gemm(c, where);                 stream
 //   void ref(gold);
-//   float host_elem(seed, row, col);     exact host value of one element,
+//   Result host_elem(seed, row, col);    exact host value of one element,
 //                                        straight from the generator
-//   std::vector<float> host_product(seed);  the whole host product, operand
+//   std::vector<Result> host_product(seed);  the whole host product, operand
 //                                        tables built once
 //   void print_product_verdict(bad_mfma, bad_gold);  the self-test's lines
 //                                        about the product, FAIL line included
@@ -28,6 +36,10 @@
 // the figures in GemmVerifyResult (the caller prints its own JSON line and
 // turns a miscompare into exit status 4); 1 on a HIP error; 3 when the
 // self-test or the gold spot-check failed.
+//
+// The compare reports 32-bit dwords. With a 4-byte Result a dword index is
+// the element index row * N + col; with double it is 2 * element + half
+// (half 0 = the low dword), and a miscompare line ends in " half 0|1".
 
 #pragma once
 
@@ -55,18 +67,20 @@ struct GemmVerifyResult {
   }
 };
 
-// fp32 C and gold of an M x N problem and the per-tile XCC_ID/HW_ID record.
+// C and gold of an M x N problem and the per-tile XCC_ID/HW_ID record.
+template <typename Result>
 struct GemmResultBufs {
-  DevBuf<float> c, gold;
+  DevBuf<Result> c, gold;
   DevBuf<int> where;
   int64_t tiles = 0;
 
-  int alloc(int64_t m, int64_t n) {
+  int alloc(int64_t m, int64_t n, int poison) {
+    const size_t bytes = (size_t)m * n * sizeof(Result);
     tiles = (m / k3samd_kern::kGemmBM) * (n / k3samd_kern::kGemmBN);
-    HIP_CHECK(c.alloc((size_t)m * n * 4));
-    HIP_CHECK(gold.alloc((size_t)m * n * 4));
+    HIP_CHECK(c.alloc(bytes));
+    HIP_CHECK(gold.alloc(bytes));
     HIP_CHECK(where.alloc((size_t)tiles * 8));
-    HIP_CHECK(hipMemset(c, 0xFF, (size_t)m * n * 4));  // NaN: unwritten != gold
+    HIP_CHECK(hipMemset(c, poison, bytes));  // unwritten != gold
     HIP_CHECK(hipMemset(where, 0xFF, (size_t)tiles * 8));
     return 0;
   }
@@ -80,34 +94,40 @@ template <typename Problem>
 int gemm_verify_selftest(Problem p, void* d_report) {
   const int64_t m = 256, n = 256, k = Problem::kSelftestK;
   const uint64_t seed = 0x5EEDF00Dull;
-  GemmResultBufs g;
-  if (p.alloc(m, n, k) || g.alloc(m, n)) return 1;
+  using Result = typename Problem::Result;
+  constexpr size_t kBytes = sizeof(Result);
+  constexpr uint64_t kDwords = kBytes / 4;  // report dwords per element
+  GemmResultBufs<Result> g;
+  if (p.alloc(m, n, k) || g.alloc(m, n, Problem::kPoison)) return 1;
   p.fill(seed);
   p.ref(g.gold);
   p.gemm(g.c, g.where);
   HIP_CHECK(hipGetLastError());
-  std::vector<float> hc(m * n), hg(m * n);
-  HIP_CHECK(hipMemcpy(hc.data(), g.c, hc.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hg.data(), g.gold, hg.size() * 4, hipMemcpyDeviceToHost));
-  const std::vector<float> want = p.host_product(seed);
+  std::vector<Result> hc(m * n), hg(m * n);
+  HIP_CHECK(hipMemcpy(hc.data(), g.c, hc.size() * kBytes,
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(hg.data(), g.gold, hg.size() * kBytes,
+                      hipMemcpyDeviceToHost));
+  const std::vector<Result> want = p.host_product(seed);
   // bitwise (stricter than !=), as the main loop compares C with the gold
   long long bad_mfma = 0, bad_gold = 0;
   for (int64_t e = 0; e < m * n; ++e) {
-    if (std::memcmp(&hc[e], &want[e], 4)) ++bad_mfma;
-    if (std::memcmp(&hg[e], &want[e], 4)) ++bad_gold;
+    if (std::memcmp(&hc[e], &want[e], kBytes)) ++bad_mfma;
+    if (std::memcmp(&hg[e], &want[e], kBytes)) ++bad_gold;
   }
   p.print_product_verdict(bad_mfma, bad_gold);
   if (bad_mfma || bad_gold) return 3;
 
   DrillFlip flips[3] = {{0, 0, 1u << 0},
                         {12345, 0, 1u << 17},
-                        {(uint64_t)(m * n - 1), 0, 1u << 31}};
+                        {(uint64_t)(m * n) * kDwords - 1, 0, 1u << 31}};
   for (DrillFlip& f : flips) {
-    std::memcpy(&f.expect, &hg[f.index], 4);
+    std::memcpy(&f.expect, (const char*)hg.data() + f.index * 4, 4);
     if (mem_flip(g.c, f.index, f.mask)) return 1;
   }
   if (mem_report_reset(d_report)) return 1;
-  k3samd_kern::launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
+  k3samd_kern::launch_buf_compare(0, g.c, g.gold, m * n * kBytes / 16,
+                                  d_report);
   HIP_CHECK(hipGetLastError());
   return drill_verdict(d_report, flips,
                        {Problem::kTag, "", "bad_elems",
@@ -122,14 +142,17 @@ int gemm_verify(Problem& p, int64_t m, int64_t n, int64_t k, int iters,
   using namespace k3samd_kern;
   const char* const tag = Problem::kTag;
   const uint64_t seed = 0;
+  using Result = typename Problem::Result;
+  constexpr size_t kBytes = sizeof(Result);
+  constexpr uint64_t kDwords = kBytes / 4;  // report dwords per element
   DevBuf<long long> d_report;
   HIP_CHECK(d_report.alloc(sizeof(long long) * kMemReportLen));
   if (selftest) {
     int rc = gemm_verify_selftest(p.fresh(), d_report);
     if (rc) return rc;
   }
-  GemmResultBufs g;
-  if (p.alloc(m, n, k) || g.alloc(m, n)) return 1;
+  GemmResultBufs<Result> g;
+  if (p.alloc(m, n, k) || g.alloc(m, n, Problem::kPoison)) return 1;
   p.fill(seed);
   // one timed launch, no warm-up
   if (EventTimer().best_of(0, 1, [&](bool) { p.ref(g.gold); }, &out->gold_ms))
@@ -142,13 +165,13 @@ int gemm_verify(Problem& p, int64_t m, int64_t n, int64_t k, int iters,
                                  : (uint32_t)(((uint64_t)i * 0x9E3779B1ull) % (uint64_t)m);
     const uint32_t col = i == 63 ? (uint32_t)(n - 1)
                                  : (uint32_t)(((uint64_t)i * 0x85EBCA6Bull + 7) % (uint64_t)n);
-    float got;
-    HIP_CHECK(hipMemcpy(&got, g.gold + (size_t)row * n + col, 4,
+    Result got;
+    HIP_CHECK(hipMemcpy(&got, g.gold + (size_t)row * n + col, kBytes,
                         hipMemcpyDeviceToHost));
-    const float want = p.host_elem(seed, row, col);
-    if (std::memcmp(&got, &want, 4)) {
+    const Result want = p.host_elem(seed, row, col);
+    if (std::memcmp(&got, &want, kBytes)) {
       std::printf("%s: gold spot-check FAIL at [%u][%u]: device %.2f, "
-                  "host %.2f\n", tag, row, col, got, want);
+                  "host %.2f\n", tag, row, col, (double)got, (double)want);
       return 3;
     }
   }
@@ -185,13 +208,15 @@ int gemm_verify(Problem& p, int64_t m, int64_t n, int64_t k, int iters,
       p.gemm(g.c, g.where);
       if (done == 0 && i == 0 && inject > 0) {
         // operator alerting drill: N single-bit flips (bit f % 32) in the
-        // first result before its compare, at elements evenly spaced from 0
+        // first result before its compare, at elements evenly spaced from
+        // 0 (of a double, in its low dword: half 0)
         const uint64_t step = (uint64_t)(m * n) / (uint64_t)inject;
         HIP_CHECK(hipDeviceSynchronize());
         for (int f = 0; f < inject; ++f)
-          if (mem_flip(g.c, (uint64_t)f * step, 1u << (f % 32))) return 1;
+          if (mem_flip(g.c, (uint64_t)f * step * kDwords, 1u << (f % 32)))
+            return 1;
       }
-      launch_buf_compare(0, g.c, g.gold, m * n / 4, d_report);
+      launch_buf_compare(0, g.c, g.gold, m * n * kBytes / 16, d_report);
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
@@ -217,15 +242,16 @@ int gemm_verify(Problem& p, int64_t m, int64_t n, int64_t k, int iters,
   std::vector<int> where((size_t)g.tiles * 2);
   HIP_CHECK(hipMemcpy(where.data(), g.where, where.size() * 4,
                       hipMemcpyDeviceToHost));
-  auto xcc_of = [&](unsigned long long elem, unsigned* hw_id) {
+  auto xcc_of = [&](unsigned long long dword, unsigned* hw_id) {
+    const unsigned long long elem = dword / kDwords;
     const int64_t row = (int64_t)(elem / (uint64_t)n), col = (int64_t)(elem % (uint64_t)n);
     const int64_t tile = (row / kGemmBM) * (n / kGemmBN) + col / kGemmBN;
     if (hw_id) *hw_id = (unsigned)where[2 * tile + 1];
     return where[2 * tile] & 0xF;
   };
   if (!out->clean()) {
-    out->first_bad_row = (long long)(r.first() / (uint64_t)n);
-    out->first_bad_col = (long long)(r.first() % (uint64_t)n);
+    out->first_bad_row = (long long)(r.first() / kDwords / (uint64_t)n);
+    out->first_bad_col = (long long)(r.first() / kDwords % (uint64_t)n);
     out->first_bad_xcc = xcc_of(r.first(), nullptr);
     std::printf("%s: MISCOMPARE - %lld element(s), %lld bit(s)\n", tag,
                 r.bad_dwords(), r.bad_bits());
@@ -233,12 +259,15 @@ int gemm_verify(Problem& p, int64_t m, int64_t n, int64_t k, int iters,
       const long long* rec = r.log(i);
       unsigned hw_id = 0;
       const int xcc = xcc_of((unsigned long long)rec[0], &hw_id);
+      const unsigned long long elem = (unsigned long long)rec[0] / kDwords;
       std::printf("C[%llu][%llu] expected 0x%08x actual 0x%08x xor 0x%08x "
-                  "xcc %d hw_id 0x%08x\n",
-                  (unsigned long long)rec[0] / (unsigned long long)n,
-                  (unsigned long long)rec[0] % (unsigned long long)n,
+                  "xcc %d hw_id 0x%08x",
+                  elem / (unsigned long long)n, elem % (unsigned long long)n,
                   (unsigned)rec[1], (unsigned)rec[2],
                   (unsigned)(rec[1] ^ rec[2]), xcc, hw_id);
+      if constexpr (kDwords == 2)
+        std::printf(" half %d", (int)((unsigned long long)rec[0] & 1));
+      std::printf("\n");
     }
   }
   return 0;

@@ -120,6 +120,8 @@ float units_to_float(int fmt, long long s) {
 // The MX problem of the driver in gemm_verify.h: packed A[M,K] and Bt[N,K]
 // of one element format with their E8M0 block scales, from mx_pattern.h.
 struct MxProblem {
+  using Result = float;
+  static constexpr int kPoison = 0xFF;  // NaN
   static constexpr const char* kTag = "mxgemmtest";
   static constexpr int64_t kSelftestK = 256;
   int fmt;

@@ -24,6 +24,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../k3samd/ops/hip/gemm_dense_kernels.h"
 #include "../../k3samd/ops/hip/gemm_kernels.h"
 #include "../../k3samd/ops/hip/memtest_kernels.h"
 #include "../../k3samd/ops/hip/stream_kernels.h"
@@ -45,6 +46,8 @@ constexpr float kScalar = 2.5f;  // the s of scale and triad
 double gbps(double bytes, float ms) { return bytes / (ms * 1e6); }
 double tflops(double flops, float ms) { return flops / (ms * 1e9); }
 
+constexpr int kNoGemmFormat = -1;
+
 struct Options {
   int64_t mib = 1024;
   int iters = 20, device = 0;
@@ -56,6 +59,10 @@ struct Options {
   bool gemmtest = false;
   int64_t gemm_m = 4096, gemm_n = 4096, gemm_k = 4096;
   int gemm_iters = 0, gemm_seconds = 0, gemm_inject = 0;
+  // --gemm-format: kNoGemmFormat without the flag, 0 = bf16, else a
+  // k3samd_kern::kGemmFmt* id; the flag's word when it names no format
+  int gemm_format = kNoGemmFormat;
+  const char* gemm_format_bad = nullptr;
 };
 
 // Numerics self-check: the pod log doubles as a correctness oracle (the
@@ -321,7 +328,8 @@ int run_memtest(const Options& o) {
 }
 
 // ---------------------------------------------------------------------------
-// --gemmtest: verified bf16 MFMA GEMM (kernels in gemm_kernels.h). The
+// --gemmtest: verified bf16 MFMA GEMM (kernels in gemm_kernels.h) or, with
+// --gemm-format, fp16 / int8 / fp32 / fp64 (gemm_dense_kernels.h). The
 // operands are small integers, so C is known exactly and compared bitwise
 // against a gold computed without the matrix pipes.
 // Exit codes: 0 clean, 3 self-test / gold spot-check failed, 4 miscompare.
@@ -353,6 +361,8 @@ int gemm_operand_dump(char** a) {
 // The bf16 problem of the driver in gemm_verify.h: bf16 A[M,K] and Bt[N,K]
 // of small integers from gemm_pattern.h.
 struct Bf16Problem {
+  using Result = float;
+  static constexpr int kPoison = 0xFF;  // NaN
   static constexpr const char* kTag = "gemmtest";
   static constexpr int64_t kSelftestK = 128;
   DevBuf<void> a, bt;
@@ -415,14 +425,83 @@ struct Bf16Problem {
   }
 };
 
-int run_gemmtest(const Options& o) {
-  Bf16Problem p;
+// The fp16 / int8 / fp32 / fp64 problem: the same operands in the format's
+// element type, C and gold in its result type (gemm_dense_kernels.h).
+template <int kFmt, typename Result_>
+struct DenseProblem {
+  using Result = Result_;
+  // -1 is a legitimate int32 product; 0x80808080 lies outside +-2^23
+  static constexpr int kPoison = kFmt == k3samd_kern::kGemmFmtInt8 ? 0x80 : 0xFF;
+  static constexpr const char* kTag = "gemmtest";
+  static constexpr int64_t kSelftestK = 2 * k3samd_kern::gemm_dense_step_k(kFmt);
+  DevBuf<void> a, bt;
+  int64_t m = 0, n = 0, k = 0;
+
+  DenseProblem fresh() const { return {}; }
+  const char* label() const {
+    using namespace k3samd_kern;
+    return kFmt == kGemmFmtFp16   ? "fp16 "
+           : kFmt == kGemmFmtInt8 ? "int8 "
+           : kFmt == kGemmFmtFp32 ? "fp32 "
+                                  : "fp64 ";
+  }
+  int alloc(int64_t m_, int64_t n_, int64_t k_) {
+    m = m_, n = n_, k = k_;
+    const size_t elem = k3samd_kern::gemm_dense_elem_bytes(kFmt);
+    HIP_CHECK(a.alloc((size_t)m * k * elem));
+    HIP_CHECK(bt.alloc((size_t)n * k * elem));
+    return 0;
+  }
+  void fill(uint64_t seed) {
+    k3samd_kern::launch_gemm_dense_fill(0, kFmt, a, 0, seed, m, k);
+    k3samd_kern::launch_gemm_dense_fill(0, kFmt, bt, 1, seed, n, k);
+  }
+  void gemm(Result* c, int* where) {
+    k3samd_kern::launch_gemm_dense_nt(0, kFmt, a, bt, c, where, m, n, k);
+  }
+  void ref(Result* gold) {
+    k3samd_kern::launch_gemm_dense_ref_int(0, kFmt, a, bt, gold, m, n, k);
+  }
+
+  // The integer products are Bf16Problem's; only the result type differs.
+  Result host_elem(uint64_t seed, uint32_t row, uint32_t col) const {
+    Bf16Problem b;
+    b.k = k;
+    return (Result)(long long)b.host_elem(seed, row, col);
+  }
+  std::vector<Result> host_product(uint64_t seed) const {
+    Bf16Problem b;
+    b.m = m, b.n = n, b.k = k;
+    const std::vector<float> f = b.host_product(seed);  // exact: <= 2^23
+    std::vector<Result> c(f.size());
+    for (size_t i = 0; i < f.size(); ++i) c[i] = (Result)(long long)f[i];
+    return c;
+  }
+  void print_product_verdict(long long bad_mfma, long long bad_gold) const {
+    const char* name = k3samd_kern::gemm_dense_fmt_name(kFmt);
+    if (bad_mfma || bad_gold)
+      std::printf("gemmtest selftest: FAIL (256x256x%lld %s vs host product: "
+                  "%lld MFMA element(s), %lld gold element(s) differ)\n",
+                  (long long)kSelftestK, name, bad_mfma, bad_gold);
+    else
+      std::printf("gemmtest selftest: 256x256x%lld %s MFMA product and integer "
+                  "gold match the host product exactly\n",
+                  (long long)kSelftestK, name);
+  }
+};
+
+// `format` is the word of --gemm-format, null without the flag: only then
+// does the JSON line carry it.
+template <typename Problem>
+int run_gemmtest_as(Problem p, const Options& o, const char* format) {
   GemmVerifyResult v;
   int rc = gemm_verify(p, o.gemm_m, o.gemm_n, o.gemm_k, o.gemm_iters,
                        o.gemm_seconds, o.gemm_inject, o.do_check, &v);
   if (rc) return rc;
+  std::printf("{\"payload\": \"mi-gemmtest\", ");
+  if (format) std::printf("\"format\": \"%s\", ", format);
   std::printf(
-      "{\"payload\": \"mi-gemmtest\", \"m\": %lld, \"n\": %lld, \"k\": %lld, "
+      "\"m\": %lld, \"n\": %lld, \"k\": %lld, "
       "\"iters\": %lld, \"bad_elems\": %lld, \"bad_bits\": %lld, "
       "\"first_bad_row\": %lld, \"first_bad_col\": %lld, "
       "\"first_bad_xcc\": %d, \"avg_tflops\": %.1f, \"gold_ms\": %.1f, "
@@ -432,6 +511,23 @@ int run_gemmtest(const Options& o) {
       v.first_bad_col, v.first_bad_xcc,
       v.tflops(o.gemm_m, o.gemm_n, o.gemm_k), v.gold_ms, v.max_temp_c, v.max_power_w, v.clean() ? "true" : "false");
   return v.clean() ? 0 : 4;
+}
+
+int run_gemmtest(const Options& o) {
+  using namespace k3samd_kern;
+  switch (o.gemm_format) {
+    case kGemmFmtFp16:
+      return run_gemmtest_as(DenseProblem<kGemmFmtFp16, float>{}, o, "fp16");
+    case kGemmFmtInt8:
+      return run_gemmtest_as(DenseProblem<kGemmFmtInt8, int32_t>{}, o, "int8");
+    case kGemmFmtFp32:
+      return run_gemmtest_as(DenseProblem<kGemmFmtFp32, float>{}, o, "fp32");
+    case kGemmFmtFp64:
+      return run_gemmtest_as(DenseProblem<kGemmFmtFp64, double>{}, o, "fp64");
+    default:
+      return run_gemmtest_as(Bf16Problem{}, o,
+                             o.gemm_format == kNoGemmFormat ? nullptr : "bf16");
+  }
 }
 
 // ---- STREAM modes ----
@@ -721,6 +817,9 @@ const char kUsage[] =
     " [--gemm-iters I | --gemm-seconds T] [--gemm-inject N]]"
     " [--gemm-operand-dump WHICH SEED ROW0 COL0 ROWS COLS]\n";
 
+// The usage line is pinned byte for byte by the CLI tests, so like
+// --no-check, --gemm-format (bf16|fp16|int8|fp32|fp64) is not on it: the
+// README, the runbook and the refusal of an unknown format name it.
 // Flags are matched left to right. The two dump flags run (host only) and
 // return as soon as they are reached; an unknown flag, or a flag short of
 // its values, prints the usage line and returns 2 (--help: 0).
@@ -752,7 +851,15 @@ int parse_options(int argc, char** argv, Options& o) {
     } else if (flag("--gemm-iters", 1)) o.gemm_iters = std::atoi(argv[++i]);
     else if (flag("--gemm-seconds", 1)) o.gemm_seconds = std::atoi(argv[++i]);
     else if (flag("--gemm-inject", 1)) o.gemm_inject = std::atoi(argv[++i]);
-    else if (flag("--gemm-operand-dump", 6))
+    else if (flag("--gemm-format", 1)) {
+      using namespace k3samd_kern;
+      const char* w = o.gemm_format_bad = argv[++i];
+      for (int f = 0; f <= kGemmFmtFp64; ++f)
+        if (!std::strcmp(w, f ? gemm_dense_fmt_name(f) : "bf16")) {
+          o.gemm_format = f;
+          o.gemm_format_bad = nullptr;
+        }
+    } else if (flag("--gemm-operand-dump", 6))
       return gemm_operand_dump(argv + i + 1);
     else return usage_status(kUsage, argv[i]);
   }
@@ -771,7 +878,27 @@ int validate_options(Options& o) {
   }
   if (o.gemmtest) {
     if (o.gemm_iters == 0 && o.gemm_seconds == 0) o.gemm_seconds = 1;
-    if (!k3samd_kern::gemm_shape_ok(o.gemm_m, o.gemm_n, o.gemm_k) ||
+    if (o.gemm_format_bad) {
+      std::fprintf(stderr, "mi-stream: --gemm-format %s: the formats are bf16"
+                           " (K-step 64), fp16 (64), int8 (128), fp32 (32),"
+                           " fp64 (16)\n", o.gemm_format_bad);
+      return 2;
+    }
+    if (o.gemm_format > 0) {  // a dense format: its own K-step
+      using namespace k3samd_kern;
+      if (!gemm_dense_shape_ok(o.gemm_format, o.gemm_m, o.gemm_n, o.gemm_k) ||
+          o.gemm_k > kGemmExactMaxK || o.gemm_iters < 0 ||
+          o.gemm_seconds < 0 || (o.gemm_iters > 0 && o.gemm_seconds > 0) ||
+          o.gemm_inject < 0 || o.gemm_inject > 16) {
+        std::fprintf(stderr, "mi-stream: --gemmtest --gemm-format %s needs M"
+                             " and N multiples of 128, K a multiple of %d and"
+                             " <= 32768, one of --gemm-iters >= 1 /"
+                             " --gemm-seconds >= 1, --gemm-inject 1..16\n",
+                     gemm_dense_fmt_name(o.gemm_format),
+                     gemm_dense_step_k(o.gemm_format));
+        return 2;
+      }
+    } else if (!k3samd_kern::gemm_shape_ok(o.gemm_m, o.gemm_n, o.gemm_k) ||
         o.gemm_k > k3samd_kern::kGemmExactMaxK || o.gemm_iters < 0 ||
         o.gemm_seconds < 0 || (o.gemm_iters > 0 && o.gemm_seconds > 0) ||
         o.gemm_inject < 0 || o.gemm_inject > 16) {
