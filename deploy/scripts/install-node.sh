@@ -23,7 +23,7 @@ fi
 
 for bin in k3samd-oci-runtime k3samd-device-plugin k3samd-node-labeller \
            k3samd-cdi-gen mi355x-smi mi-stream mi-allreduce mi-mxgemm \
-           mi-cutest mi-hostlink; do
+           mi-cutest mi-hostlink mi-atomtest; do
   if [ -x "$repo_root/native/bin/$bin" ]; then
     install -m 0755 "$repo_root/native/bin/$bin" "$PREFIX/$bin"
     echo "installed $PREFIX/$bin"

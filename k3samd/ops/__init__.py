@@ -413,6 +413,143 @@ def link_chase_expected(n, seed, hops):
         int(n), int(seed) & _U64, int(hops)))
 
 
+# ---- global-atomics integrity test (kernels in hip/atom_kernels.h) ----
+# A slot is one 4- or 8-byte element of `buf`; W contributors (workgroups)
+# each apply one operand of hip/atom_pattern.h to every slot. Report dword
+# indices count 32-bit words of the buffer (two per 8-byte slot, low first).
+
+ATOM_MAX_CONTRIBUTORS = 4096
+ATOM_MAX_PACKED = 240
+ATOM_TILE = 256  # slots per tile = lanes per workgroup
+ATOM_CHAIN_OPS = ("swap", "swap64", "cas", "cas64")
+
+
+def _atom_ops():
+    try:
+        import torch
+    except ImportError:
+        return {}
+    i32, i64 = torch.int32, torch.int64
+    table = {}
+    for name in ("add", "and", "or", "xor", "smin", "smax", "umin", "umax"):
+        table[name] = (i32, 4, "global_atomic_" + name, ATOM_MAX_CONTRIBUTORS)
+    for name in ("add", "and", "or", "xor", "smin", "smax", "umin", "umax"):
+        table[name + "64"] = (i64, 8, f"global_atomic_{name}_x2",
+                              ATOM_MAX_CONTRIBUTORS)
+    table["addf32"] = (torch.float32, 4, "global_atomic_add_f32",
+                       ATOM_MAX_CONTRIBUTORS)
+    table["addf64"] = (torch.float64, 8, "global_atomic_add_f64",
+                       ATOM_MAX_CONTRIBUTORS)
+    table["minf64"] = (torch.float64, 8, "global_atomic_min_f64",
+                       ATOM_MAX_CONTRIBUTORS)
+    table["maxf64"] = (torch.float64, 8, "global_atomic_max_f64",
+                       ATOM_MAX_CONTRIBUTORS)
+    table["pkaddbf16"] = (i32, 4, "global_atomic_pk_add_bf16", ATOM_MAX_PACKED)
+    table["pkaddf16"] = (i32, 4, "global_atomic_pk_add_f16", ATOM_MAX_PACKED)
+    table["swap"] = (i32, 4, "global_atomic_swap", ATOM_MAX_CONTRIBUTORS)
+    table["swap64"] = (i64, 8, "global_atomic_swap_x2", ATOM_MAX_CONTRIBUTORS)
+    table["cas"] = (i32, 4, "global_atomic_cmpswap", ATOM_MAX_CONTRIBUTORS)
+    table["cas64"] = (i64, 8, "global_atomic_cmpswap_x2",
+                      ATOM_MAX_CONTRIBUTORS)
+    return table
+
+
+# name -> (tensor dtype of a slot buffer, slot bytes, the instruction the op
+# compiles to, W cap). The order is the native op id; the last four are the
+# chain ops (their "W" is the round count). A packed slot is two 16-bit
+# floats in an int32.
+ATOM_OPS = _atom_ops()
+ATOM_REDUCE_OPS = tuple(n for n in ATOM_OPS if n not in ATOM_CHAIN_OPS)
+
+
+def atom_op_id(op) -> int:
+    """Native id of an op given by name (or already by id)."""
+    if isinstance(op, str):
+        try:
+            return list(ATOM_OPS).index(op)
+        except ValueError:
+            raise ValueError(f"unknown atomics op {op!r}") from None
+    return int(op)
+
+
+def atom_fill(buf, op, seed):
+    """Store atom_init(op, seed, slot) into every slot of `buf` with plain
+    stores."""
+    _require_native().atom_fill(buf, atom_op_id(op), int(seed) & _U64)
+
+
+def atom_gold(buf, op, seed, W):
+    """Store atom_expected(op, seed, slot, W) into every slot: one thread
+    per slot folds the operands in registers, no atomic is issued."""
+    _require_native().atom_gold(buf, atom_op_id(op), int(seed) & _U64, int(W))
+
+
+def atom_reduce(buf, op, seed, W, rotate=False, returning=False, gold=None,
+                report=None, drop=None):
+    """W workgroups each apply their operand to every slot of `buf` with
+    the op's atomic instruction. `rotate` starts workgroup w at tile
+    (40503 * w) % tiles; `drop` = (w, tile) makes that workgroup skip that
+    tile. `returning` uses the value-returning form and checks each returned
+    value against the final value in `gold` (order-independent invariants),
+    accumulating violations into `report`."""
+    dw, dt = (-1, -1) if drop is None else (int(drop[0]), int(drop[1]))
+    _require_native().atom_reduce(buf, atom_op_id(op), int(seed) & _U64, int(W),
+                                  bool(rotate), bool(returning), gold, report,
+                                  dw, dt)
+
+
+def atom_ticket(counters, tickets, where):
+    """Draw i of len(tickets) takes a ticket from counter i % len(counters)
+    with a returning fetch-add and stores it in tickets[i]. `counters` (int32
+    or int64, zeroed by the caller) and `tickets` share a dtype; `where`
+    (int32 [ceil(draws / 256), 2]) receives each workgroup's placement."""
+    _require_native().atom_ticket(counters, tickets, where)
+
+
+def atom_ticket_check(counters, tickets, perm, report):
+    """Prove without atomics that each counter's tickets are a permutation
+    of 0..n-1 and that it ended at n. `perm` (int32 [C * ceil(draws / C)])
+    is scratch. Report dword c * ceil(draws / C) + t is (counter c, ticket
+    t): expected t; dword C * ceil(draws / C) + c is counter c's final
+    value."""
+    _require_native().atom_ticket_check(counters, tickets, perm, report)
+
+
+def atom_chain_round(buf, op, seed, round, report, where):
+    """Round `round` of swap / swap64 / cas / cas64: every slot moves from
+    v_round to v_round+1 with one returning atomic (cas: after one that must
+    fail) and the returned value is checked into `report`. `where` (int32
+    [wgs, 2]) sets the grid; tile t is served by workgroup (t + round) %
+    wgs."""
+    _require_native().atom_chain_round(buf, atom_op_id(op), int(seed) & _U64,
+                                       int(round), report, where)
+
+
+def atom_init(op, seed, slot) -> int:
+    """Bits a slot holds before any atomic, from the host code of
+    hip/atom_pattern.h. Needs no GPU."""
+    return _require_native().atom_init(atom_op_id(op), int(seed) & _U64,
+                                       int(slot) & _U64)
+
+
+def atom_operand(op, seed, slot, w, W) -> int:
+    """Bits contributor `w` of `W` applies to a slot. Needs no GPU."""
+    return _require_native().atom_operand(atom_op_id(op), int(seed) & _U64,
+                                          int(slot) & _U64, int(w), int(W))
+
+
+def atom_expected(op, seed, slot, W) -> int:
+    """Bits of the slot after all W contributors. Needs no GPU."""
+    return _require_native().atom_expected(atom_op_id(op), int(seed) & _U64,
+                                           int(slot) & _U64, int(W))
+
+
+def atom_shape_ok(op, slots, W) -> bool:
+    """The caps every entry point applies: 1 <= slots <= 2^30 and 1 <= W <=
+    the op's cap."""
+    return _require_native().atom_shape_ok(atom_op_id(op), int(slots), int(W))
+
+
 def mem_report_read(report) -> MemReport:
     """Copy the report to the host (this is the synchronisation point)."""
     return _mem_report_decode(report.cpu().tolist())

@@ -8,6 +8,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "atom_kernels.h"
 #include "cu_test_kernels.h"
 #include "gemm_dense_kernels.h"
 #include "gemm_kernels.h"
@@ -351,6 +352,84 @@ void check_chase_buf(const torch::Tensor& t, int64_t n) {
 void check_link_threads(int64_t threads) {
   K3_CHECK(threads >= 0 && threads <= k3samd_kern::kLinkMaxHostThreads,
            "threads must be 0 (automatic) .. 16");
+}
+
+
+// ---- global-atomics test arguments (atom_kernels.h) ----
+// Everything that does not need the device is checked before the device
+// checks, and all of it before any launch.
+
+void check_atom_op(int64_t op, bool reduce) {
+  K3_CHECK(k3samd_kern::atom_op_ok((int)op) && op == (int)op,
+           "unknown atomics op id (see ops.ATOM_OPS)");
+  K3_CHECK(k3samd_kern::atom_is_chain((int)op) != reduce,
+           reduce ? "op must be a reduce op, not swap / cas"
+                  : "op must be a chain op: swap, swap64, cas or cas64");
+}
+
+// A slot buffer of `op`: contiguous, elements of the op's slot size, within
+// atom_shape_ok(op, slots, w). Returns the slot count.
+int64_t check_atom_buf(const torch::Tensor& t, int64_t op, int64_t w) {
+  K3_CHECK(t.is_contiguous(), "buffer must be contiguous");
+  K3_CHECK((int64_t)t.element_size() == k3samd_kern::atom_slot_bytes((int)op),
+           "buffer element size must be the op's slot size (4 or 8 bytes)");
+  K3_CHECK(k3samd_kern::atom_shape_ok((int)op, t.numel(), w),
+           "atomics shape contract: 1 <= slots <= 2^30, 1 <= W <= the op's "
+           "cap (240 packed, else 4096)");
+  return t.numel();
+}
+
+void check_atom_report(const torch::Tensor& report, const torch::Tensor& buf) {
+  check_report_shape(report);
+  K3_CHECK(buf.is_cuda(), "buffer must be on GPU");
+  K3_CHECK(report.is_cuda() && report.device() == buf.device(),
+           "report must be on the same GPU as the buffer");
+}
+
+// int32 [wgs, 2] placement table on the buffer's GPU; returns wgs.
+int64_t check_atom_where(const torch::Tensor& where, int64_t wgs_exact,
+                         int64_t wgs_max) {
+  K3_CHECK(where.scalar_type() == torch::kInt32, "where must be int32");
+  K3_CHECK(where.dim() == 2 && where.size(1) == 2 && where.is_contiguous() &&
+               where.size(0) >= 1 && where.size(0) <= wgs_max &&
+               (wgs_exact == 0 || where.size(0) == wgs_exact),
+           wgs_exact ? "where must be a contiguous int32[ceil(draws/256),2]"
+                     : "where must be a contiguous int32[wgs,2], 1 <= wgs <= "
+                       "65536");
+  return where.size(0);
+}
+
+struct AtomTicketDims {
+  int64_t counters, draws;
+  bool wide;
+};
+
+AtomTicketDims check_atom_ticket(const torch::Tensor& counters,
+                                 const torch::Tensor& tickets) {
+  K3_CHECK((counters.scalar_type() == torch::kInt32 ||
+            counters.scalar_type() == torch::kInt64) &&
+               tickets.scalar_type() == counters.scalar_type(),
+           "counters and tickets must both be int32 or both int64");
+  K3_CHECK(counters.dim() == 1 && tickets.dim() == 1 &&
+               counters.is_contiguous() && tickets.is_contiguous(),
+           "counters and tickets must be contiguous and one-dimensional");
+  K3_CHECK(counters.numel() >= 1 &&
+               counters.numel() <= k3samd_kern::kAtomMaxCounters &&
+               tickets.numel() >= 1 &&
+               tickets.numel() <= k3samd_kern::kAtomMaxDraws,
+           "1 <= counters <= 2^20 and 1 <= draws <= 2^30");
+  return {counters.numel(), tickets.numel(),
+          counters.scalar_type() == torch::kInt64};
+}
+
+// `other` is the where or perm table of the same call.
+void check_atom_ticket_devices(const torch::Tensor& counters,
+                               const torch::Tensor& tickets,
+                               const torch::Tensor& other, const char* msg) {
+  K3_CHECK(counters.is_cuda() && tickets.is_cuda() &&
+               counters.device() == tickets.device(),
+           "counters and tickets must be on the same GPU");
+  K3_CHECK(other.is_cuda() && other.device() == counters.device(), msg);
 }
 
 }  // namespace
@@ -907,6 +986,155 @@ std::tuple<int64_t, int64_t> link_chase_expected(int64_t n, uint64_t seed,
   return {(int64_t)r.final_index, (int64_t)r.xor_all};
 }
 
+// ---- global-atomics integrity test (atom_kernels.h, atom_pattern.h) ----
+// Like the memtest ops none of these synchronises with the host.
+
+void atom_fill(torch::Tensor buf, int64_t op, uint64_t seed) {
+  K3_CHECK(k3samd_kern::atom_op_ok((int)op) && op == (int)op,
+           "unknown atomics op id (see ops.ATOM_OPS)");
+  const int64_t slots = check_atom_buf(buf, op, 1);
+  K3_CHECK(buf.is_cuda(), "buffer must be on GPU");
+  k3samd_kern::launch_atom_fill(at::hip::getCurrentHIPStream(), buf.data_ptr(),
+                                slots, (int)op, seed);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void atom_gold(torch::Tensor buf, int64_t op, uint64_t seed, int64_t W) {
+  K3_CHECK(k3samd_kern::atom_op_ok((int)op) && op == (int)op,
+           "unknown atomics op id (see ops.ATOM_OPS)");
+  const int64_t slots = check_atom_buf(buf, op, W);
+  K3_CHECK(buf.is_cuda(), "buffer must be on GPU");
+  k3samd_kern::launch_atom_gold(at::hip::getCurrentHIPStream(), buf.data_ptr(),
+                                slots, (int)op, seed, (int)W);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void atom_reduce(torch::Tensor buf, int64_t op, uint64_t seed, int64_t W,
+                 bool rotate, bool returning,
+                 c10::optional<torch::Tensor> gold,
+                 c10::optional<torch::Tensor> report, int64_t drop_w,
+                 int64_t drop_tile) {
+  check_atom_op(op, true);
+  k3samd_kern::AtomReduceArgs a{};
+  a.slots = check_atom_buf(buf, op, W);
+  const int64_t tiles =
+      (a.slots + k3samd_kern::kAtomTile - 1) / k3samd_kern::kAtomTile;
+  K3_CHECK((drop_w == -1 && drop_tile == -1) ||
+               (drop_w >= 0 && drop_w < W && drop_tile >= 0 &&
+                drop_tile < tiles),
+           "drop must be None or (w < W, tile < tiles)");
+  K3_CHECK(returning == gold.has_value() && returning == report.has_value(),
+           "returning=True needs gold and report; returning=False takes "
+           "neither");
+  if (returning) {
+    K3_CHECK(gold->is_contiguous() &&
+                 gold->element_size() == buf.element_size() &&
+                 gold->numel() == buf.numel(),
+             "gold must have the buffer's slot size and slot count");
+    check_atom_report(*report, buf);
+    K3_CHECK(gold->is_cuda() && gold->device() == buf.device(),
+             "gold must be on the same GPU as the buffer");
+    a.gold = gold->data_ptr();
+    a.report = report->data_ptr();
+  }
+  K3_CHECK(buf.is_cuda(), "buffer must be on GPU");
+  a.buf = buf.data_ptr();
+  a.seed = seed;
+  a.W = (int)W;
+  a.rotate = rotate;
+  a.drop_w = drop_w;
+  a.drop_tile = drop_tile;
+  k3samd_kern::launch_atom_reduce(at::hip::getCurrentHIPStream(), (int)op, a);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// `counters` must be zero; `where` int32 [ceil(draws / 256), 2].
+void atom_ticket(torch::Tensor counters, torch::Tensor tickets,
+                 torch::Tensor where) {
+  const AtomTicketDims d = check_atom_ticket(counters, tickets);
+  check_atom_where(where, k3samd_kern::atom_grid(d.draws), 1ll << 22);
+  check_atom_ticket_devices(counters, tickets, where,
+                            "where must be on the same GPU as the counters");
+  k3samd_kern::launch_atom_ticket(at::hip::getCurrentHIPStream(), d.wide,
+                                  counters.data_ptr(), d.counters,
+                                  tickets.data_ptr(), d.draws,
+                                  where.data_ptr());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// `perm` int32 [counters * ceil(draws / counters)], overwritten.
+void atom_ticket_check(torch::Tensor counters, torch::Tensor tickets,
+                       torch::Tensor perm, torch::Tensor report) {
+  const AtomTicketDims d = check_atom_ticket(counters, tickets);
+  K3_CHECK(perm.scalar_type() == torch::kInt32 && perm.is_contiguous() &&
+               perm.numel() == k3samd_kern::atom_ticket_perm_words(d.draws,
+                                                                   d.counters),
+           "perm must be a contiguous int32 tensor of counters * "
+           "ceil(draws / counters) elements");
+  check_report_shape(report);
+  check_atom_ticket_devices(counters, tickets, perm,
+                            "perm must be on the same GPU as the counters");
+  check_atom_report(report, counters);
+  C10_HIP_CHECK(k3samd_kern::launch_atom_ticket_check(
+      at::hip::getCurrentHIPStream(), d.wide, counters.data_ptr(), d.counters,
+      tickets.data_ptr(), d.draws, perm.data_ptr(), report.data_ptr()));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// One round of a chain op; `where` int32 [wgs, 2] sets the grid.
+void atom_chain_round(torch::Tensor buf, int64_t op, uint64_t seed,
+                      int64_t round, torch::Tensor report,
+                      torch::Tensor where) {
+  check_atom_op(op, false);
+  const int64_t slots = check_atom_buf(buf, op, 1);
+  K3_CHECK(round >= 0 && round < k3samd_kern::atom_w_cap((int)op),
+           "round must be in 0 .. 4095");
+  const int64_t wgs = check_atom_where(where, 0, k3samd_kern::kAtomMaxChainWgs);
+  check_atom_report(report, buf);
+  K3_CHECK(where.is_cuda() && where.device() == buf.device(),
+           "where must be on the same GPU as the buffer");
+  k3samd_kern::launch_atom_chain(at::hip::getCurrentHIPStream(), (int)op,
+                                 buf.data_ptr(), slots, seed, (uint32_t)round,
+                                 report.data_ptr(), where.data_ptr(), (int)wgs);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// Host code only (atom_pattern.h): bit patterns as unsigned integers.
+void check_atom_pattern_args(int64_t op, int64_t w, int64_t W) {
+  K3_CHECK(k3samd_kern::atom_op_ok((int)op) && op == (int)op,
+           "unknown atomics op id (see ops.ATOM_OPS)");
+  K3_CHECK(W >= 1 && W <= k3samd_kern::atom_w_cap((int)op) && w >= 0 && w < W,
+           "0 <= w < W and 1 <= W <= the op's cap (240 packed, else 4096)");
+}
+
+uint64_t atom_init(int64_t op, uint64_t seed, uint64_t slot) {
+  check_atom_pattern_args(op, 0, 1);
+  return k3samd_kern::atom_init((int)op, seed, slot);
+}
+
+uint64_t atom_operand(int64_t op, uint64_t seed, uint64_t slot, int64_t w,
+                      int64_t W) {
+  check_atom_pattern_args(op, w, W);
+  return k3samd_kern::atom_operand((int)op, seed, slot, (uint32_t)w,
+                                   (uint32_t)W);
+}
+
+uint64_t atom_expected(int64_t op, uint64_t seed, uint64_t slot, int64_t W) {
+  check_atom_pattern_args(op, 0, W);
+  return k3samd_kern::atom_expected((int)op, seed, slot, (uint32_t)W);
+}
+
+bool atom_shape_ok(int64_t op, int64_t slots, int64_t W) {
+  return op == (int)op && k3samd_kern::atom_shape_ok((int)op, slots, W);
+}
+
+std::vector<std::string> atom_op_names() {
+  std::vector<std::string> names;
+  for (int op = 0; op < k3samd_kern::kAtomOpCount; ++op)
+    names.emplace_back(k3samd_kern::atom_op_name(op));
+  return names;
+}
+
 // Host-side query: the extension only ships gfx950 code objects, so report
 // whether the active device is gfx950.
 bool has_mfma() {
@@ -1004,6 +1232,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed"));
   m.def("link_chase_expected", &link_chase_expected, py::arg("n"),
         py::arg("seed"), py::arg("hops"));
+  m.def("atom_fill", &atom_fill, py::arg("buf"), py::arg("op"),
+        py::arg("seed"));
+  m.def("atom_gold", &atom_gold, py::arg("buf"), py::arg("op"),
+        py::arg("seed"), py::arg("W"));
+  m.def("atom_reduce", &atom_reduce, py::arg("buf"), py::arg("op"),
+        py::arg("seed"), py::arg("W"), py::arg("rotate") = false,
+        py::arg("returning") = false, py::arg("gold") = py::none(),
+        py::arg("report") = py::none(), py::arg("drop_w") = -1,
+        py::arg("drop_tile") = -1);
+  m.def("atom_ticket", &atom_ticket, py::arg("counters"), py::arg("tickets"),
+        py::arg("where"));
+  m.def("atom_ticket_check", &atom_ticket_check, py::arg("counters"),
+        py::arg("tickets"), py::arg("perm"), py::arg("report"));
+  m.def("atom_chain_round", &atom_chain_round, py::arg("buf"), py::arg("op"),
+        py::arg("seed"), py::arg("round"), py::arg("report"),
+        py::arg("where"));
+  m.def("atom_init", &atom_init, py::arg("op"), py::arg("seed"),
+        py::arg("slot"));
+  m.def("atom_operand", &atom_operand, py::arg("op"), py::arg("seed"),
+        py::arg("slot"), py::arg("w"), py::arg("W"));
+  m.def("atom_expected", &atom_expected, py::arg("op"), py::arg("seed"),
+        py::arg("slot"), py::arg("W"));
+  m.def("atom_shape_ok", &atom_shape_ok, py::arg("op"), py::arg("slots"),
+        py::arg("W"));
+  m.def("atom_op_names", &atom_op_names);
+  m.attr("ATOM_REDUCE_OPS") = (int64_t)k3samd_kern::kAtomReduceOps;
   m.attr("LINK_DEFAULT_WGS") = (int64_t)k3samd_kern::kLinkDefaultWgs;
   m.attr("LINK_MAX_WGS") = (int64_t)k3samd_kern::kLinkMaxWgs;
   m.attr("MEM_REPORT_LEN") =(int64_t)k3samd_kern::kMemReportLen;
